@@ -7,7 +7,9 @@ fixed random target, at BASELINE config 4 shape (DyNeRF cook_spinach: 300k Gauss
 config, all five heads).  N GPUs = N independent frames per step (weak scaling) + one RCCL all-reduce of the loss
 statistics.  Synthetic scene: no datasets/checkpoints exist offline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times exactly K steps and prints the headline; --dump-outputs writes what the last timed step computed;
+--full adds per-kernel times, rooflines, frame statistics, the secondary figures and the CPU baseline with oracle parity.
 N > 1: either launched by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment) or, when
 WORLD_SIZE is unset, bench.py spawns its N ranks itself (parallel.spawn_local: one process per GPU, rank r -> cuda:r, RCCL
 rendezvous on 127.0.0.1) and fails with a clear message when fewer than N GPUs are visible.
@@ -75,10 +77,14 @@ def main():
     ap.add_argument("--scene", default="cube", choices=["cube", "shell"],
                     help="synthetic scene: cube = SURVEY 8d's generator (a volume that occludes itself: ~13 %% of the visible Gaussians get a "
                          "gradient), shell = surface-like translucent scene (three thin spheres, opacity U(0.02, 0.2): ~98 %% do)")
-    ap.add_argument("--repeats", type=int, default=0, help="timed regions of exactly --steps steps each; value = median; "
+    ap.add_argument("--repeats", type=int, default=1, help="timed regions of exactly --steps steps each; value = median; "
                     "0 = as many back-to-back regions as give >= 2 s of GPU work (at least 5, at most 80)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary figures (forward-only, random order, all-tiles "
+    ap.add_argument("--no-extras", action="store_true", help="skip the secondary figures of --full (forward-only, random order, all-tiles "
                     "backward, reorder cost, train iteration, batched step)")
+    ap.add_argument("--full", action="store_true", help="after the headline also measure per-kernel times, rooflines, frame statistics, the "
+                    "secondary figures (unless --no-extras) and the CPU baseline with oracle parity (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (image, depth, radii, "
+                    "loss statistics, every gradient; a fixed sample of the per-Gaussian rows) as DIR/<name>.npy")
     args = ap.parse_args()
     args.no_extras = args.no_extras or args.no_train_step
 
@@ -189,6 +195,8 @@ def run(args, make_step=None):
     st = fdgs._lib.stream_ptr
     ptr = fdgs._lib.ptr
     info = {}
+    full = getattr(args, "full", False)
+    dump_dir = getattr(args, "dump_outputs", None) if rank == 0 else None
 
     def make_render_step(model):
         prm = [p for p in model.parameters() if p.requires_grad]
@@ -208,6 +216,8 @@ def run(args, make_step=None):
             img.backward(dimg)
             pending[b_] = par.allreduce_loss_stats(acc_, async_op=True)   # the only cross-GPU exchange of the path, under the next step
             info["radii"], info["vsp"], info["vis"], info["acc"] = res["radii"], res["viewspace_points"], res["visibility_filter"], acc_
+            if dump_dir:
+                info["res"] = res
             return acc_
         return step
 
@@ -237,6 +247,24 @@ def run(args, make_step=None):
     l1, psnr = par.loss_from_stats(info.get("acc", acc).clone())
     fps = world * args.steps / dt
     ms_regions = [x / args.steps * 1e3 for x in regions]
+    if dump_dir:
+        dump_outputs(dump_dir, info["res"], pc, info["acc"])
+        del info["res"]
+    head = {
+        "metric": "train-step frames/sec (fwd+bwd raster+deform)", "value": fps, "unit": "frames/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic", "src_sha16": lib_sha16(fdgs),
+        "config": {"workload": args.workload, "scene": scene, "gaussians": N, "image": [W, H], "deformation": dcfg,
+                   "frames_per_step": world, "gaussian_order": args.order, "parallelism": f"frame-parallel x{world}"},
+        "p10_ms_per_step": _percentile(ms_regions, 0.1), "p90_ms_per_step": _percentile(ms_regions, 0.9),
+        "timed_regions": len(regions), "timed_regions_ms_per_step": [round(x, 4) for x in ms_regions], "value_is": "median of the timed regions",
+        "ranks_seen": ranks_seen, "per_rank_ms_per_step": [round(x, 4) for x in per_rank_ms],
+        "startup_s_per_rank": [round(x, 2) for x in per_rank_startup], "loss": {"l1": float(l1), "psnr": float(psnr)}, "full": full,
+    }
+    if not full:
+        if rank == 0:
+            print(json.dumps(head))
+        return
 
     # ---- per-kernel timing with HIP events on the launch stream (separate instrumented pass over the same steps)
     import ctypes
@@ -289,7 +317,6 @@ def run(args, make_step=None):
     stage_bytes = algorithmic_bytes(N, R, W * H, G, d_sh)
     B_frame = sum(stage_bytes.values())
     flops_fwd = mlp_flops_fwd(cfg) * N
-    ms_step = dt / args.steps * 1e3
     # work models per kernel.  Backward-data FLOPs: with saved activations (default) the kernel only does the backward products
     # proper -- dh1 = W2^T G (2 W k), dW2 = G^T h1 (2 W k), dhid += W1^T dh1 (2 W^2) per head, dfeat = W0^T dhid (2 F W); without them
     # it also recomputes the forward (trunk + the heads' hidden layers).  Both backward kernels only run over the LIVE tiles
@@ -518,22 +545,15 @@ def run(args, make_step=None):
 
     if rank == 0:
         out = {
-            "metric": "train-step frames/sec (fwd+bwd raster+deform)", "value": fps, "unit": "frames/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "src_sha16": lib_sha16(fdgs),
-            "config": {"workload": args.workload, "scene": scene, "gaussians": N, "image": [W, H], "deformation": dcfg,
-                       "frames_per_step": world, "gaussian_order": args.order, "parallelism": f"frame-parallel x{world}", "num_rendered": R, "visible": V,
+            **head,
+            "config": {**head["config"], "num_rendered": R, "visible": V,
                        "backward_live_tiles": {"live": live_tiles, "tiles": all_tiles, "frac": round(live_frac, 4),
                                                "what": "32-row units the deformation backward walked, of the 32-Gaussian tiles there are: units of the list "
                                                        "of non-zero gradient ROWS (padded to whole chunks) where the row-list form runs -- saved activations, "
                                                        "ordered input, knob row_compact -- else the tiles with a non-zero row.  The other Gaussians are culled / "
                                                        "off-screen / occluded: zero rows, which add exactly zero and are skipped; mean of 8 frames"}},
             "roofline": roof, "rooflines": rooflines, "cpu_baseline": cpu, "parity": parity,
-            "p10_ms_per_step": _percentile(ms_regions, 0.1), "p90_ms_per_step": _percentile(ms_regions, 0.9),
-            "timed_regions": len(regions), "timed_regions_ms_per_step": [round(x, 4) for x in ms_regions], "value_is": "median of the timed regions",
-            **extras, "train_iteration": train, "batched_step": batched,
-            "ranks_seen": ranks_seen, "per_rank_ms_per_step": [round(x, 4) for x in per_rank_ms],
-            "startup_s_per_rank": [round(x, 2) for x in per_rank_startup], "ranks": ranks,
+            **extras, "train_iteration": train, "batched_step": batched, "ranks": ranks,
             "frame_hbm": {"algorithmic_bytes": B_frame, "achieved_GBps": B_frame / (dt / args.steps / 1) / 1e9 if world == 1 else None,
                           "frac_of_8TBps": (B_frame / (dt / args.steps)) / HBM_PEAK if world == 1 else None,
                           "note": ("algorithmic bytes per frame < 256 MiB Infinity Cache at this size: the HBM fraction is structurally small"
@@ -549,7 +569,6 @@ def run(args, make_step=None):
                                 "kernel, the rest of the frame stays queued) and finishes an overflowing frame exactly before returning (capacity_reruns); "
                                 "mode capacity (opt-in) never waits and would drop the farthest pairs of an overflowing frame (capacity_overflows)"},
             "gpu_kernel_ms_per_step": round(kernel_sum, 4),
-            "loss": {"l1": float(l1), "psnr": float(psnr)},
         }
         print(json.dumps(out))
 
@@ -706,6 +725,41 @@ def cpu_baseline(fdgs, syn, pc, cam, target, dcfg, frames, deformed=None):
             "sample": f"{frames} full frame(s) of the same workload (fwd+bwd), {dt:.1f} s wall on {threads} threads of {cores} host cores; "
                       "deformation = oracle pinned to the reference modules (torch CPU), rasterizer = our C restatement (OpenMP)",
             "stage_seconds": {k_: round(v_, 3) for k_, v_ in stage.items()}}, ref)
+
+
+DUMP_BUDGET_BYTES = 64_000_000     # --dump-outputs writes at most this much in all
+DUMP_ROWS = 65536                  # per-Gaussian arrays: this many rows, one fixed seeded sample shared by all of them
+DUMP_ARRAY_BYTES = 16 << 20        # any other array larger than this: a fixed seeded sample of its elements
+
+
+def dump_outputs(out_dir, res, pc, acc):
+    """What the timed step hands its caller, as float32 .npy files: render() outputs, the loss statistics, the gradient of every parameter
+    and of the screen-space means.  Same arguments -> same inputs and the same sampled rows / elements, so two builds compare file by file."""
+    import numpy as np
+    n = pc._xyz.shape[0]
+    rows = None
+    if n > DUMP_ROWS:
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(1234))[:DUMP_ROWS].sort().values.to(pc._xyz.device)
+    arrays = {"render": res["render"], "depth": res["depth"], "radii": res["radii"], "loss_stats": acc,
+              "grad.viewspace_points": res["viewspace_points"].grad}
+    # (parameters the render path does not use -- the time net -- receive no gradient, as in the reference: nothing to write)
+    arrays.update({"grad." + k: p_.grad for k, p_ in pc.named_parameters() if p_.requires_grad and p_.grad is not None})
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        if t is None:
+            raise RuntimeError(f"--dump-outputs: {name} was not computed by the timed step")
+        t = t.detach()
+        if rows is not None and t.dim() >= 1 and t.shape[0] == n:
+            t = t.index_select(0, rows)
+        elif t.numel() * 4 > DUMP_ARRAY_BYTES:
+            k = DUMP_ARRAY_BYTES // 4
+            t = t.reshape(-1).index_select(0, torch.randperm(t.numel(), generator=torch.Generator().manual_seed(4321))[:k].sort().values.to(t.device))
+        a = t.float().cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_BUDGET_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_BUDGET_BYTES} bytes at {name}")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def hip_deformed(fdgs, pc, cam):

@@ -1,14 +1,14 @@
 """CPU: the Python surface mirrors the reference's by name -- same parameter names, order and defaults as the functions /
-methods it replaces (checked against the reference sources where /root/reference is present, against the recorded
-parameter lists everywhere)."""
+methods it replaces (checked against the recorded parameter lists and against the signatures the reference sources had when
+tests/golden/reference_checks.npz was generated)."""
 import importlib
 import inspect
-import os
 
 import pytest
 
+import reference_checks as RC
+
 fdgs = importlib.import_module("4dgaussians_amd")
-REF = "/root/reference"
 
 # (our callable, recorded parameter list of the reference callable, reference "module:qualname" or None)
 def _cases():
@@ -44,28 +44,25 @@ def test_signature_matches_recorded_reference_signature(ours, recorded, ref):
     assert _sig(ours) == recorded
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
 def test_recorded_signatures_match_the_reference_sources():
-    from oracle import densify_oracle, loss_oracle
-    lu = loss_oracle.import_reference_loss_utils()
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("_ref_image_utils", os.path.join(REF, "utils", "image_utils.py"))
-    iu = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(iu)
+    """Against the signatures of the reference's own functions / methods (tests/golden/reference_checks.npz, generated from the reference
+    sources by tests/golden/make_reference_checks_golden.py)."""
+    Z = RC.load()
+    ref = lambda name: [str(x) for x in Z["sig." + name]]
     L, D = fdgs.losses, fdgs.densify
-    for ours, theirs in ((L.l1_loss, lu.l1_loss), (L.l2_loss, lu.l2_loss), (L.ssim, lu.ssim), (L.psnr, iu.psnr), (L.mse, iu.mse)):
-        assert _sig(ours) == _sig(theirs), ours.__name__
-    GM = densify_oracle.import_reference_gaussian_model()
+    for ours, theirs in ((L.l1_loss, "l1_loss"), (L.l2_loss, "l2_loss"), (L.ssim, "ssim"), (L.psnr, "psnr"), (L.mse, "mse")):
+        assert _sig(ours) == ref(theirs), ours.__name__
+    GM = lambda name: ref("GaussianModel." + name)
     # method(self, ...) <-> function(pc, ...): same names after the first; our extra trailing keyword arguments are optional
-    for ours, theirs in ((D.add_densification_stats, GM.add_densification_stats), (D.prune_points, GM.prune_points), (D.prune, GM.prune),
-                         (D.reset_opacity, GM.reset_opacity), (D.densify, GM.densify), (fdgs.io.save_ply, GM.save_ply),
-                         (fdgs.io.load_ply, GM.load_ply), (fdgs.io.save_deformation, GM.save_deformation), (fdgs.io.load_model, GM.load_model)):
-        a, b = _sig(ours)[1:], _sig(theirs)[1:]
+    for ours, theirs in ((D.add_densification_stats, GM("add_densification_stats")), (D.prune_points, GM("prune_points")), (D.prune, GM("prune")),
+                         (D.reset_opacity, GM("reset_opacity")), (D.densify, GM("densify")), (fdgs.io.save_ply, GM("save_ply")),
+                         (fdgs.io.load_ply, GM("load_ply")), (fdgs.io.save_deformation, GM("save_deformation")), (fdgs.io.load_model, GM("load_model"))):
+        a, b = _sig(ours)[1:], theirs[1:]
         # same names in the same order; a default of the reference is our default too (ours may add defaults, never drop one)
         assert [x.split("=")[0] for x in a[:len(b)]] == [x.split("=")[0] for x in b], (ours.__name__, a, b)
         assert all(x == y for x, y in zip(a, b) if "=" in y), (ours.__name__, a, b)
         assert all("=" in extra for extra in a[len(b):]), (ours.__name__, a[len(b):])
-    assert _sig(fdgs.compute_regulation)[1:] == _sig(GM.compute_regulation)[1:]
+    assert _sig(fdgs.compute_regulation)[1:] == GM("compute_regulation")[1:]
     # the settings tuple and the rasterizer call of the un-vendored CUDA wheel, as the reference uses them by keyword
     # (gaussian_renderer/__init__.py:38-58, 120-128)
     assert list(fdgs.GaussianRasterizationSettings._fields) == ["image_height", "image_width", "tanfovx", "tanfovy", "bg", "scale_modifier", "viewmatrix",

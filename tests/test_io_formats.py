@@ -10,7 +10,6 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import deform_oracle as DO
 
 io = importlib.import_module("4dgaussians_amd.io")
 fdgs = importlib.import_module("4dgaussians_amd")
@@ -109,14 +108,23 @@ def test_deformation_checkpoint_round_trip_and_key_compatibility(tmp_path):
     assert pc2._deformation_table.all() and not pc2._deformation_accum.any()
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/scene/deformation.py"), reason="reference tree not present")
 @pytest.mark.parametrize("cfg", ["dnerf_bouncingballs", "hypernerf_default", "dynerf_default"])
 def test_deformation_pth_interchanges_with_the_reference_module(tmp_path, cfg):
-    """deformation.pth written from our module loads into the reference's deform_network (strict) and vice versa."""
+    """deformation.pth written from our module has the layout of the reference's deform_network state dict (its keys, in order, with
+    shapes and dtypes: what a strict load into the reference checks), and a file of that layout loads into our module (strict).  The
+    reference's layout is recorded in tests/golden/reference_checks.npz."""
+    import reference_checks as RC
+    layout = [str(x) for x in RC.load()[f"layout.{cfg}"]]
     args = syn.deform_args(cfg)
-    ours, ref = fdgs.deform_network(args), DO.import_reference_deform_network()(args)
+    ours = fdgs.deform_network(args)
     torch.save(ours.state_dict(), tmp_path / "ours.pth")
-    torch.save(ref.state_dict(), tmp_path / "ref.pth")
-    ref.load_state_dict(torch.load(tmp_path / "ours.pth"), strict=True)
+    assert [RC.layout_entry(k, v) for k, v in torch.load(tmp_path / "ours.pth").items()] == layout
+    dtypes = {str(d): d for d in (torch.float32, torch.float64, torch.int64, torch.bool)}
+    ref_sd = {}
+    for entry in layout:
+        k, shape, dt = entry.split("|")
+        ref_sd[k] = torch.ones(eval(shape), dtype=dtypes[dt])
+    torch.save(ref_sd, tmp_path / "ref.pth")
     ours.load_state_dict(torch.load(tmp_path / "ref.pth"), strict=True)
-    assert list(ours.state_dict().keys()) == list(ref.state_dict().keys())
+    assert list(ours.state_dict().keys()) == list(ref_sd.keys())
+    assert all(torch.equal(v, ref_sd[k]) for k, v in ours.state_dict().items())

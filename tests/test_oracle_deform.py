@@ -1,5 +1,5 @@
-"""Pins oracle/deform_oracle.py against the reference's own modules (imported from /root/reference when present,
-SURVEY.md Appendix E) and against committed golden vectors generated from them (tests/golden/)."""
+"""Pins oracle/deform_oracle.py against the reference's own modules through committed golden vectors generated
+from them (tests/golden/)."""
 import importlib
 import os
 
@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import have_reference
+import reference_checks as RC
 from oracle import deform_oracle as DO
 
 synthetic = importlib.import_module("4dgaussians_amd.synthetic")
@@ -20,35 +20,32 @@ def _inputs(n, seed=1):
     return g["xyz"], g["scaling"], g["rotation"], g["opacity"], shs
 
 
-@pytest.mark.skipif(not have_reference(), reason="/root/reference not present (GPU box)")
 @pytest.mark.parametrize("cfg", ["dnerf_bouncingballs", "hypernerf_default", "dynerf_default"])
 def test_matches_reference_modules_fwd_bwd(cfg):
-    deform_network = DO.import_reference_deform_network()
-    torch.manual_seed(6666)
+    """The reference's deform_network, loaded with a seeded network of this repository (grids perturbed), evaluated forward and
+    backward on seeded Gaussians: its outputs and every gradient are recorded in tests/golden/reference_deform_<cfg>.npz."""
+    Z = RC.load(RC.deform_path(cfg))
     args = synthetic.deform_args(cfg)
-    net = deform_network(args)
-    with torch.no_grad():
-        for name, p in net.named_parameters():
-            if "grids" in name:
-                p.add_(0.1 * torch.randn_like(p))
-    n = 257
-    xyz, sc, rot, op, shs = [x.clone().requires_grad_(True) for x in _inputs(n)]
-    net.deformation_net.set_aabb(xyz.max(0).values.tolist(), xyz.min(0).values.tolist())
-    t = torch.rand(n, 1)
-    ref = net(xyz, sc, rot, op, shs, t)
+    net = importlib.import_module("4dgaussians_amd").deform_network(args)
+    net.load_state_dict(RC.seeded_deform_state(cfg), strict=True)
+    xyz, sc, rot, op, shs, t = [x.clone().requires_grad_(i < 5) for i, x in enumerate(RC.deform_inputs())]
+    ref = [torch.from_numpy(Z[f"deform.{cfg}.out{i}"]) for i in range(5)]
     sd = {k: v for k, v in net.named_parameters()}
     sd.update({k: v for k, v in net.named_buffers()})
     ora = DO.deform_forward(sd, args, xyz, sc, rot, op, shs, t)
+    assert len(ora) == len(ref)
     for a, b in zip(ref, ora):
         assert torch.allclose(a, b, rtol=1e-5, atol=1e-6)
-    ws = [torch.randn_like(a) for a in ref]
+    ws = RC.deform_weights(ref)
+    names = ["in.xyz", "in.scales", "in.rot", "in.opacity", "in.shs"] + [k for k, p in net.named_parameters() if p.requires_grad]
     params = [p for p in net.parameters() if p.requires_grad]
-    gr = torch.autograd.grad(sum((a * w).sum() for a, w in zip(ref, ws)), [xyz, sc, rot, op, shs] + params, allow_unused=True)
     go = torch.autograd.grad(sum((a * w).sum() for a, w in zip(ora, ws)), [xyz, sc, rot, op, shs] + params, allow_unused=True)
-    for a, b in zip(gr, go):
-        assert (a is None) == (b is None)
-        if a is not None:
-            assert torch.allclose(a, b, rtol=1e-4, atol=1e-5), float((a - b).abs().max())
+    for name, b in zip(names, go):
+        key = f"deform.{cfg}.grad.{name}"
+        assert (key in Z.files) == (b is not None), name
+        if b is not None:
+            a = torch.from_numpy(Z[key])
+            assert torch.allclose(a, b, rtol=1e-4, atol=1e-5), (name, float((a - b).abs().max()))
 
 
 @pytest.mark.parametrize("cfg", ["dnerf_bouncingballs", "hypernerf_default", "dynerf_default"])

@@ -1,12 +1,13 @@
 """CPU: the densification oracle (oracle/densify_oracle.py) against the golden vector produced by the reference's own
-GaussianModel methods (tests/golden/make_densify_golden.py) and, where /root/reference is present, against those methods
-run live on CPU."""
+GaussianModel methods (tests/golden/make_densify_golden.py) and against what those methods computed on further seeded states
+(tests/golden/reference_checks.npz)."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import reference_checks as RC
 from oracle import densify_oracle as DO
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "densify_small.npz")
@@ -53,20 +54,17 @@ def test_oracle_reproduces_the_reference_sequence_of_the_golden_vector():
     assert_states_equal(st, load_state(g, "reset"))
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/scene/gaussian_model.py"), reason="reference tree not present")
 @pytest.mark.parametrize("n,seed,size", [(300, 3, 20), (64, 4, None), (1, 5, 20)])
 def test_oracle_matches_reference_methods_live(n, seed, size):
+    """The reference's GaussianModel.densify / prune on the same seeded state and normal samples: its states after each are recorded in
+    tests/golden/reference_checks.npz (tests/golden/make_reference_checks_golden.py)."""
+    i = RC.DENSIFY_CASES.index((n, seed, size))
+    g = RC.load()
     st = DO.random_state(n, seed, sh_rest=3)
     normals = torch.randn(2 * n, 3, generator=torch.Generator().manual_seed(seed))
-    m = DO.reference_model_from_state(st, 0.01)
     o = DO.clone_state(st)
-    with DO.reference_on_cpu(normals):
-        m.densify(0.0002, 0.005, 3.0, size, 5, 5)
-        DO.densify(o, 0.0002, 3.0, 0.01, normals)
-        assert_states_equal(o, DO.state_from_reference_model(m))
-        r = torch.rand(m.get_xyz.shape[0], generator=torch.Generator().manual_seed(seed + 1)) * 40
-        m.max_radii2D = r.clone()
-        o["max_radii2D"] = r.clone()
-        m.prune(0.0002, 0.05, 3.0, size)
-        DO.prune(o, 0.05, 3.0, size)
-        assert_states_equal(o, DO.state_from_reference_model(m))
+    DO.densify(o, 0.0002, 3.0, 0.01, normals)
+    assert_states_equal(o, load_state(g, f"densify{i}_densified"))
+    o["max_radii2D"] = torch.rand(o["param"]["xyz"].shape[0], generator=torch.Generator().manual_seed(seed + 1)) * 40
+    DO.prune(o, 0.05, 3.0, size)
+    assert_states_equal(o, load_state(g, f"densify{i}_pruned"))

@@ -1,11 +1,13 @@
 """CPU: the image-loss oracle (oracle/loss_oracle.py) against the committed golden vector generated from the reference's own
-utils/loss_utils.py (tests/golden/make_loss_golden.py) and, where /root/reference is present, against that code directly."""
+utils/loss_utils.py (tests/golden/make_loss_golden.py) and against what that code computed on further seeded images
+(tests/golden/reference_checks.npz)."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import reference_checks as RC
 from oracle import loss_oracle as LO
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loss_ssim.npz")
@@ -35,17 +37,17 @@ def test_oracle_float64_agrees_with_float32():
     assert abs(LO.ssim(b32.double(), b32.double()).item() - 1.0) < 1e-12   # identical images
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/utils/loss_utils.py"), reason="reference tree not present")
 @pytest.mark.parametrize("shape", [(1, 3, 11, 11), (2, 3, 40, 64), (1, 1, 5, 70)])
 def test_oracle_matches_reference_functions(shape):
-    ref = LO.import_reference_loss_utils()
-    gen = torch.Generator().manual_seed(sum(shape))
-    a = torch.rand(*shape, generator=gen).requires_grad_(True)
-    b = torch.rand(*shape, generator=gen)
-    for avg in (True, False):
-        r, o = ref.ssim(a, b, size_average=avg), LO.ssim(a, b, size_average=avg)
-        assert torch.allclose(r, o, atol=3e-6), (r, o)
-    gr, = torch.autograd.grad(ref.ssim(a, b), a)
+    """Against the reference's own ssim / l1_loss on the same seeded images (recorded in tests/golden/reference_checks.npz)."""
+    g = RC.load()
+    key = "loss." + "x".join(map(str, shape))
+    a, b = RC.loss_inputs(shape)
+    a.requires_grad_(True)
+    for avg, name in ((True, "ssim_avg"), (False, "ssim_items")):
+        r, o = torch.from_numpy(g[f"{key}.{name}"]), LO.ssim(a, b, size_average=avg)
+        assert r.shape == o.shape and torch.allclose(r, o, atol=3e-6), (r, o)
+    gr = torch.from_numpy(g[key + ".grad_ssim"])
     go, = torch.autograd.grad(LO.ssim(a, b), a)
     assert (gr - go).norm() / gr.norm() < 1e-5
-    assert abs(ref.l1_loss(a, b).item() - LO.l1_loss(a, b).item()) < 1e-7
+    assert abs(float(g[key + ".l1"]) - LO.l1_loss(a, b).item()) < 1e-7

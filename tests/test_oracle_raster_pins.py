@@ -1,6 +1,6 @@
 """Partial pin of the (otherwise unpinned) rasterizer oracle: every piece of the rasterizer's arithmetic that the reference
-ALSO holds in-tree as python is compared with the reference's own functions -- live where /root/reference exists, and through
-the committed fixture tests/golden/raster_pins.npz (generator: tests/golden/make_raster_pins_golden.py) everywhere:
+ALSO holds in-tree as python is compared with the reference's own functions through the committed fixture
+tests/golden/raster_pins.npz (generator: tests/golden/make_raster_pins_golden.py):
   cov3D from scale/rotation (utils/general_utils.py:63-116 + scene/gaussian_model.py:29-34), world-to-view / projection /
   camera centre (utils/graphics_utils.py:38-71, scene/cameras.py:59-64), SH -> colour (utils/sh_utils.py:57-112 as render()
   uses it, gaussian_renderer/__init__.py:106-111).
@@ -13,7 +13,6 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import have_reference
 from oracle import raster_torch
 from oracle.raster_oracle import RasterOracle
 
@@ -93,18 +92,12 @@ def test_sh_colours_match_reference(deg):
     np.testing.assert_allclose(o.field("rgb")[vis], Z[f"sh.colors.deg{deg}"][vis], rtol=0, atol=2e-6)
 
 
-@pytest.mark.skipif(not have_reference(), reason="/root/reference not present (GPU box)")
 def test_fixture_is_what_the_reference_computes_now():
-    """Live re-evaluation of the reference functions (guards the committed fixture against drift)."""
-    from oracle import densify_oracle as DN
-    DN.import_reference_gaussian_model()
-    import utils.general_utils as gu
-    from utils.graphics_utils import getProjectionMatrix, getWorld2View2
-    s, q = torch.tensor(Z["cov.scales"]), torch.tensor(Z["cov.rotations_raw"])
-    with DN.reference_on_cpu():
-        L = gu.build_scaling_rotation(0.7 * s, q)
-        cov = gu.strip_symmetric(L @ L.transpose(1, 2))
-    np.testing.assert_array_equal(cov.numpy(), Z["cov3D.mod0.7"])
-    np.testing.assert_array_equal(getWorld2View2(Z["cam1.R"], Z["cam1.T"]), Z["cam1.w2v"])
+    """A second evaluation of the reference functions on the fixture's inputs (tests/golden/reference_checks.npz, generated separately by
+    tests/golden/make_reference_checks_golden.py) guards the committed fixture against drift."""
+    import reference_checks as RC
+    R = RC.load()
+    np.testing.assert_array_equal(R["pins.cov3D.mod0.7"], Z["cov3D.mod0.7"])
+    np.testing.assert_array_equal(R["pins.cam1.w2v"], Z["cam1.w2v"])
     cam = synthetic.make_camera(1352, 1014, theta_deg=-60.0)
-    np.testing.assert_array_equal(getProjectionMatrix(0.01, 100.0, cam.FoVx, cam.FoVy).numpy(), Z["cam1.proj"])
+    np.testing.assert_array_equal(R["pins.cam1.proj"], Z["cam1.proj"])

@@ -2,7 +2,7 @@
 mkdir -p gpurun_out; OUT=gpurun_out/${1:-r06c_d2x}.txt; : > $OUT
 for v in "" $(ls tools/_variants/libfdgs_x_*.so); do
   for sc in shell; do
-    FDGS_LIB=${v:+$PWD/$v} timeout 300 python bench.py --no-extras --no-cpu-baseline --steps 20 --warmup 6 --repeats 6 --scene $sc > /tmp/v.json 2>/tmp/v.err
+    FDGS_LIB=${v:+$PWD/$v} timeout 300 python bench.py --full --no-extras --no-cpu-baseline --steps 20 --warmup 6 --repeats 6 --scene $sc > /tmp/v.json 2>/tmp/v.err
     python - "${v:-base}" $sc >> $OUT <<'PY'
 import json, sys
 try:

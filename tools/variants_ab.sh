@@ -11,7 +11,7 @@ run() {  # name, env assignments..., -- bench args
   local envs=()
   while [ "$1" != "--" ]; do envs+=("$1"); shift; done
   shift
-  env "${envs[@]}" timeout 200 python bench.py --no-extras --no-cpu-baseline --steps 20 --warmup 6 --repeats 12 "$@" > /tmp/v.json 2> /tmp/v.err || { echo "$name FAILED: $(tail -2 /tmp/v.err)" >> $OUT; return; }
+  env "${envs[@]}" timeout 200 python bench.py --full --no-extras --no-cpu-baseline --steps 20 --warmup 6 --repeats 12 "$@" > /tmp/v.json 2> /tmp/v.err || { echo "$name FAILED: $(tail -2 /tmp/v.err)" >> $OUT; return; }
   python - "$name" "$@" >> $OUT <<'PY'
 import json, sys
 d = json.load(open("/tmp/v.json"))
