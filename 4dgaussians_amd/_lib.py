@@ -135,7 +135,12 @@ SYMBOLS = {
                                   c_float, c_float, c_float, c_float, c_float, c_void_p, POINTER(c_uint32)]),
     "fdgs_densify_apply": (c_int, [c_void_p, POINTER(GaussiansIn), POINTER(GaussiansOut), c_void_p, c_void_p]),
     "fdgs_permute_rows": (c_int, [c_void_p, c_int, c_void_p, c_int, POINTER(RowArray), c_int]),
+    "fdgs_spatial_order_scratch_bytes": (c_int, [c_int, POINTER(c_size_t)]),
+    "fdgs_spatial_keys": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "fdgs_spatial_order": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "fdgs_spatial_keys_host": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
 }
+CURVES = {"hilbert": 0, "morton": 1}      # FDGS_CURVE_*
 
 ABI_VERSION = 6       # what this Python host was written against (include/fdgs.h); checked when the library is loaded
 

@@ -337,11 +337,11 @@ def implicit_permutation(xyz, aabb=None):
         return e[2]
     from . import densify as _densify
     with torch.no_grad():
+        # (fdgs.densify.spatial_order: the library's key kernel + radix sort for float32 positions on the device, torch otherwise)
         if aabb is not None and aabb.device == xyz.device:
-            keys = _densify.hilbert_keys(xyz, aabb[1], aabb[0])          # aabb[0] = max, aabb[1] = min (scene/hexplane.py:19-20)
+            perm = _densify.spatial_order(xyz, aabb[1], aabb[0])         # aabb[0] = max, aabb[1] = min (scene/hexplane.py:19-20)
         else:
-            keys = _densify.hilbert_keys(xyz)
-        perm = torch.argsort(keys, stable=True).to(torch.int32).contiguous()
+            perm = _densify.spatial_order(xyz)
     _cache_put(_perm_cache, xyz, key, perm)
     return perm
 

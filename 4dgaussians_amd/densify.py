@@ -278,6 +278,75 @@ def hilbert_keys(xyz, lo=None, hi=None, bits=10):
     return (_spread3(X[0]) << 2) | (_spread3(X[1]) << 1) | _spread3(X[2])
 
 
+# The keys and their stable argsort as HIP kernels of the library (csrc/spatial.hip: fdgs_spatial_keys / fdgs_spatial_order -- the key
+# function above restated bit for bit, binning.hip's radix sort) for contiguous float32 positions on a HIP device; everything else (CPU
+# tensors, other dtypes) and FDGS_NATIVE_ORDER=0 take the torch expressions above.  Same keys, same permutation either way.
+NATIVE_ORDER = os.environ.get("FDGS_NATIVE_ORDER", "1") != "0"
+_order_scratch = {}      # (device index, stream) -> ONE grow-only uint8 buffer (never keyed by size)
+
+
+def _native(xyz):
+    return NATIVE_ORDER and xyz.device.type == "cuda" and xyz.dtype == torch.float32 and xyz.is_contiguous() and xyz.dim() == 2 and xyz.shape[1] == 3
+
+
+def _order_scratch_for(xyz, n):
+    nbytes = ctypes.c_size_t()
+    check(_lib.lib().fdgs_spatial_order_scratch_bytes(n, ctypes.byref(nbytes)))
+    key = (xyz.device.index, torch.cuda.current_stream(xyz.device).cuda_stream)
+    buf = _order_scratch.get(key)
+    if buf is None or buf.numel() < nbytes.value:
+        buf = _order_scratch[key] = torch.empty(nbytes.value + nbytes.value // 4, dtype=torch.uint8, device=xyz.device)
+    return buf
+
+
+def _native_bounds(xyz, lo, hi):
+    """The two corners as one device float[2][3] (None when neither is given: the library reduces the bounding box itself)."""
+    if lo is None and hi is None:
+        return None
+    p = xyz.detach()
+    lo = p.min(0).values if lo is None else torch.as_tensor(lo, device=p.device, dtype=torch.float32)
+    hi = p.max(0).values if hi is None else torch.as_tensor(hi, device=p.device, dtype=torch.float32)
+    return torch.stack((lo.reshape(3), hi.reshape(3))).contiguous()
+
+
+def _curve(curve):
+    if curve not in _lib.CURVES:
+        raise ValueError(f"curve must be one of {sorted(_lib.CURVES)}")
+    return _lib.CURVES[curve]
+
+
+def spatial_keys(xyz, lo=None, hi=None, curve="hilbert", bits=10):
+    """hilbert_keys / morton_keys of `xyz` (int64, as they return them); one launch of the library's key kernel for contiguous float32
+    positions on a HIP device (module switch NATIVE_ORDER), the torch expressions otherwise -- the same values."""
+    cid = _curve(curve)
+    if not _native(xyz):
+        return (hilbert_keys if curve == "hilbert" else morton_keys)(xyz, lo, hi, bits)
+    n = xyz.shape[0]
+    bounds = _native_bounds(xyz, lo, hi)
+    keys = torch.empty(max(n, 1), dtype=torch.int32, device=xyz.device)[:n]
+    with torch.cuda.device(xyz.device):
+        scratch = _order_scratch_for(xyz, n) if bounds is None else None
+        check(_lib.lib().fdgs_spatial_keys(stream_ptr(), n, ptr(xyz), ptr(bounds), cid, int(bits), ptr(scratch), keys.data_ptr()))
+    return keys.to(torch.int64)
+
+
+def spatial_order(xyz, lo=None, hi=None, curve="hilbert", bits=10):
+    """The permutation that puts `xyz` in curve order (new row i = old row perm[i]): the STABLE ascending argsort of spatial_keys(...), int32, on
+    xyz's device.  Natively (fdgs_spatial_order: key kernel + LSD radix passes with the row index as payload, no torch launch, no
+    synchronisation) under the conditions of spatial_keys; torch.argsort(keys, stable=True) otherwise -- the same permutation."""
+    cid = _curve(curve)
+    if not _native(xyz):
+        keys = (hilbert_keys if curve == "hilbert" else morton_keys)(xyz, lo, hi, bits)
+        return torch.argsort(keys, stable=True).to(torch.int32).contiguous()
+    n = xyz.shape[0]
+    bounds = _native_bounds(xyz, lo, hi)
+    perm = torch.empty(max(n, 1), dtype=torch.int32, device=xyz.device)[:n]
+    with torch.cuda.device(xyz.device):
+        scratch = _order_scratch_for(xyz, n)
+        check(_lib.lib().fdgs_spatial_order(stream_ptr(), n, ptr(xyz), ptr(bounds), cid, int(bits), ptr(scratch), perm.data_ptr(), None))
+    return perm
+
+
 def spatial_reorder(pc, perm=None, curve="hilbert"):
     """Re-order the Gaussian set along a Hilbert (default) or Morton curve of the canonical positions, or by the given
     permutation.
@@ -295,25 +364,45 @@ def spatial_reorder(pc, perm=None, curve="hilbert"):
     without an optimizer (evaluation, synthetic scenes) has its Parameters' storage replaced in place.  Returns the
     permutation (new row i = old row perm[i])."""
     xyz = pc._xyz
+    perm32 = None
     if perm is None:
         aabb = None
         try:
             aabb = pc._deformation.deformation_net.grid.aabb
         except AttributeError:
             pass
-        keyfn = hilbert_keys if curve == "hilbert" else morton_keys
+        curve = "hilbert" if curve == "hilbert" else "morton"
         if aabb is not None and aabb.device == xyz.device:
-            keys = keyfn(xyz, aabb[1], aabb[0])              # aabb[0] = max, aabb[1] = min (scene/hexplane.py:19-20)
+            perm32 = spatial_order(xyz, aabb[1], aabb[0], curve)     # aabb[0] = max, aabb[1] = min (scene/hexplane.py:19-20)
         else:
-            keys = keyfn(xyz)
-        perm = torch.argsort(keys, stable=True)
+            perm32 = spatial_order(xyz, curve=curve)
+        perm = perm32.long()
     perm = perm.to(xyz.device)
     opt = getattr(pc, "optimizer", None)
     groups = _groups(pc) if opt is not None else None
     from . import deformation as _deformation
+    # On the device every float32 array with one row per Gaussian -- the six parameters, their Adam moments, the float side arrays -- moves
+    # through fdgs_permute_rows, eight arrays per launch, instead of one index_select each (the same values); the rest keeps index_select.
+    moved = {}
+    if NATIVE_ORDER and xyz.device.type == "cuda" and perm.shape[0]:
+        cand = [getattr(pc, ATTR[n]) for n in GROUPS]
+        if opt is not None:
+            for n in GROUPS:
+                st = opt.state.get(getattr(pc, ATTR[n]), None)
+                cand += [st[k] for k in ("exp_avg", "exp_avg_sq") if st is not None and k in st]
+        cand += [getattr(pc, name, None) for name in ("xyz_gradient_accum", "denom", "max_radii2D", "_deformation_accum")]
+        cand = [t for t in cand if isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == xyz.device and t.dim() >= 1
+                and t.shape[0] == perm.shape[0]]
+        if perm32 is None:
+            perm32 = perm.to(torch.int32).contiguous()
+        moved = {id(t): o for t, o in zip(cand, _deformation.permute_rows(perm32, [t.detach() for t in cand]))}
+
+    def take(t):        # `t` in the new order (t: the object the model / the optimizer holds)
+        out = moved.get(id(t))
+        return out if out is not None else t.detach().index_select(0, perm.to(t.device)).contiguous()
     for n in GROUPS:
         old = getattr(pc, ATTR[n])
-        data = old.detach().index_select(0, perm).contiguous()
+        data = take(old)
         if opt is None:
             with torch.no_grad():
                 old.data = data
@@ -325,7 +414,7 @@ def spatial_reorder(pc, perm=None, curve="hilbert"):
         if st is not None:
             for k in ("exp_avg", "exp_avg_sq"):
                 if k in st:
-                    st[k] = st[k].index_select(0, perm).contiguous()
+                    st[k] = take(st[k])
             del opt.state[old]
             opt.state[new] = st
         groups[n]["params"][0] = new
@@ -333,5 +422,5 @@ def spatial_reorder(pc, perm=None, curve="hilbert"):
     for name in ("xyz_gradient_accum", "denom", "max_radii2D", "_deformation_accum", "_deformation_table"):
         t = getattr(pc, name, None)
         if isinstance(t, torch.Tensor) and t.dim() >= 1 and t.shape[0] == perm.shape[0]:
-            setattr(pc, name, t.index_select(0, perm.to(t.device)).contiguous())
+            setattr(pc, name, take(t))
     return perm

@@ -36,8 +36,11 @@ IMPLICIT_ORDER_MIN_N = 8192
 
 
 def _implicit_perm(pc, cfg, dn):
-    if IMPLICIT_ORDER and not cfg["ordered"] and pc._xyz.shape[0] >= IMPLICIT_ORDER_MIN_N and pc._xyz.dtype == torch.float32:
-        return _deformation.implicit_permutation(pc._xyz, dn.grid.aabb)
+    if IMPLICIT_ORDER and not cfg["ordered"] and pc._xyz.shape[0] >= IMPLICIT_ORDER_MIN_N:
+        # fdgs_permute_rows moves rows of 4-byte elements: a model that keeps any of these in another dtype (half-precision SH, say) takes
+        # the unpermuted path, which accepts them
+        if all(t.dtype == torch.float32 for t in (pc._xyz, pc._scaling, pc._rotation, pc._opacity, pc._features_dc, pc._features_rest)):
+            return _deformation.implicit_permutation(pc._xyz, dn.grid.aabb)
     return None
 
 

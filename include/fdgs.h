@@ -46,7 +46,7 @@ int fdgs_timing_report(char* buf, size_t buflen, int reset);
 /* Development / test knobs (ABI 4; ten since ABI 5, eleven since round 6).  The library holds ONE table of integer knobs; it is filled from the environment variables
  * FDGS_<NAME> once, when the library is loaded, and afterwards changes only through fdgs_tuning_set -- no entry point reads the
  * environment.  Knobs select between equivalent kernel forms or launch shapes (same results up to summation order), never semantics:
- *   d1_form (16 | 32), d1_wgs, d1_split, skip_dead, d4_mfma, d4_rows_kb, tile_cull (0 = the reference's rectangle lists), rbwd_ppl (-1 = by image size | 4 | 2 | 0),
+ *   d1_form (0 | 8 | 16 | 32), d1_wgs, d1_split, skip_dead, d4_mfma, d4_rows_kb, tile_cull (0 = the reference's rectangle lists), rbwd_ppl (-1 = by image size | 4 | 2 | 0),
  *   tile_order (1 = the blending kernels take their tiles heaviest-first, 0 = image order), row_compact (1 = the deformation backward walks
  *   the non-zero rows instead of the non-zero 32-row tiles where it can; 2 = the same with the row lists built by the two-launch form),
  *   d2_form (0 = the weight-stationary backward-data kernel where it applies -- row lists, net_width 128, C*L 32 or 48, five heads or position + scale + rotation --, 32 = the
@@ -445,6 +445,37 @@ int fdgs_densify_apply(void* stream, const fdgs_gaussians_in* in, const fdgs_gau
 #define FDGS_MAX_ROW_ARRAYS 8
 typedef struct fdgs_row_array { const void* src; void* dst; int width; } fdgs_row_array;
 int fdgs_permute_rows(void* stream, int N, const int32_t* perm, int narrays, const fdgs_row_array* arrays, int scatter);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Spatial order (additions to ABI 6; no existing signature changed): the permutation fdgs_permute_rows needs, produced by the
+ * library -- the space-filling-curve key of every position and the STABLE ascending argsort of those keys (csrc/spatial.hip).
+ *   key: per axis, lo = min / hi = max of the two bound rows, cell = trunc(clamp((p - lo) / max(hi - lo, 1e-20) * 2^bits, 0, 2^bits - 1))
+ *        with the quotient correctly rounded to float32; the three cells go through Skilling's transpose algorithm (Hilbert) or are
+ *        interleaved x -> bit 0, y -> bit 1, z -> bit 2 (Morton), spread to the 30-bit layout.  bits = 1 .. 10; a key uses 3 * bits bits.
+ *        Bit for bit what fdgs.densify.hilbert_keys / morton_keys compute with torch on the host.
+ *   bounds_opt: device float[2][3], two opposite corners of the box in either row order (the reference's HexPlaneField.aabb as it is);
+ *        NULL = the bounding box of the points, reduced on the device into `scratch` (no read-back).
+ *   scratch: fdgs_spatial_order_scratch_bytes(N) bytes of device memory (contents unspecified before and after; one per stream).
+ *        fdgs_spatial_keys needs it only when bounds_opt is NULL.
+ *   N = 0 succeeds and writes nothing.  N < 0, bits outside 1 .. 10, an unknown curve or a NULL required pointer return FDGS_E_INVALID
+ *   with a message.  A non-finite coordinate is quantised to cell 0 of its axis (and left out of the bounding box).
+ *   All launches go on `stream`; nothing synchronises.
+ * A raw binding keeps its set ordered like the Python host does: after the set changed, fdgs_spatial_order -> fdgs_permute_rows over every
+ * per-Gaussian array (scatter = 0) -> fdgs_deform_grads::spatially_ordered = 1.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define FDGS_CURVE_HILBERT 0
+#define FDGS_CURVE_MORTON  1
+/* host-only size query (works without a GPU, like fdgs_geom_bytes) */
+int fdgs_spatial_order_scratch_bytes(int N, size_t* bytes);
+/* keys[N] (uint32) of xyz[N,3] */
+int fdgs_spatial_keys(void* stream, int N, const float* xyz, const float* bounds_opt, int curve, int bits,
+                      void* scratch, uint32_t* keys);
+/* perm[N] (int32): new row i = old row perm[i] = the STABLE ascending argsort of those keys (equal keys keep their row order);
+ * sorted_keys_opt[N] (= keys[perm[i]]) may be NULL */
+int fdgs_spatial_order(void* stream, int N, const float* xyz, const float* bounds_opt, int curve, int bits,
+                       void* scratch, int32_t* perm, uint32_t* sorted_keys_opt);
+/* the same key function evaluated on the HOST over host arrays (bounds_opt NULL = bounding box): diagnostics / tests, no GPU */
+int fdgs_spatial_keys_host(int N, const float* xyz, const float* bounds_opt, int curve, int bits, uint32_t* keys);
 
 #ifdef __cplusplus
 }
