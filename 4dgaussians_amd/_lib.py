@@ -91,6 +91,13 @@ class RowArray(Structure):
 
 MAX_ROW_ARRAYS = 8
 
+
+class BlendStream(Structure):
+    _fields_ = [("a", c_void_p), ("b", c_void_p), ("out", c_void_p), ("n_floats", c_size_t)]
+
+
+MAX_BLEND_STREAMS = 4
+
 # every symbol include/fdgs.h declares: (restype, argtypes)
 SYMBOLS = {
     "fdgs_last_error": (c_char_p, []),
@@ -139,8 +146,15 @@ SYMBOLS = {
     "fdgs_spatial_keys": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "fdgs_spatial_order": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "fdgs_spatial_keys_host": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "fdgs_state_blend": (c_int, [c_void_p, c_float, c_int, POINTER(BlendStream), c_int, c_void_p, c_void_p, c_void_p]),
+    "fdgs_state_blend_host": (c_int, [c_float, c_int, POINTER(BlendStream), c_int, c_void_p, c_void_p, c_void_p]),
+    "fdgs_pack_ply_rows": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fdgs_pack_ply_rows_host": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fdgs_image_rgb8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "fdgs_image_rgb8_host": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 CURVES = {"hilbert": 0, "morton": 1}      # FDGS_CURVE_*
+RGB8_MODES = {"trunc": 0, "round": 1}     # FDGS_RGB8_*
 
 ABI_VERSION = 6       # what this Python host was written against (include/fdgs.h); checked when the library is loaded
 

@@ -1,0 +1,286 @@
+"""Baked playback: render a trained 4D model from deformed states that stay resident in device memory.
+
+The deformed, activated state of the Gaussians depends on the frame time only, never on the camera.  `render.py`'s loop, a viewer or a
+video orbit re-evaluate the HexPlane gather and the deformation MLP for every frame all the same; `bake` runs them ONCE per timestamp and
+`Baked.render` is the rasterizer alone (stages 1-4 of include/fdgs.h) on the stored state:
+
+    baked = fdgs.playback.bake(gaussians, times)                              # once: len(times) deformation forwards
+    for cam in cameras:
+        out = baked.render(cam, pipe, background, rgb8="trunc")               # render.py:57-70 -- out["render"], out["rgb8"]
+
+    fdgs.playback.export_ply_sequence(gaussians, times, out_dir)              # export_perframe_3DGS.py: one static 3DGS PLY per time
+
+A frame time between two baked timestamps is one extra launch (fdgs_state_blend: linear in every field, sign-aligned and renormalised
+for the quaternions) or the nearer baked frame (`interp="nearest"`).  At a baked timestamp the image is bit for bit the one
+`fdgs.render(...)` returns under `torch.no_grad()`.  No gradient flows through any of this.
+
+Memory: 236 bytes per Gaussian and timestamp with all five heads on (59 floats), 40 bytes with the dnerf / hypernerf defaults (no_do,
+no_dshs: opacity and SH do not change with time and are stored once); `bake_bytes` is the exact figure, `bake(..., max_bytes=)` refuses
+before it allocates.
+"""
+import bisect
+import math
+import os
+
+import torch
+
+from . import _lib
+from . import deformation as _deformation
+from . import io as _io
+from . import rasterizer as _rasterizer
+from . import renderer as _renderer
+from .rasterizer import GaussianRasterizationSettings
+
+FIELDS = ("xyz", "scales", "rotations", "opacity", "shs")          # in the order of deformation.HEAD_NAMES: head h moves field h
+FIELD_WIDTH = _deformation.HEAD_K                                   # floats per Gaussian: 3, 3, 4, 1, 48
+FIELD_SHAPE = ((3,), (3,), (4,), (1,), (16, 3))
+# every stored array starts on a multiple of this many floats (256 bytes, what the allocator gives a tensor of its own; fdgs_state_blend
+# needs 16 bytes): the slot stride is padded, N * width is never assumed to be a multiple of anything
+SLOT_ALIGN_FLOATS = 64
+
+
+def _slot_floats(N, width):
+    return (N * width + SLOT_ALIGN_FLOATS - 1) // SLOT_ALIGN_FLOATS * SLOT_ALIGN_FLOATS
+
+
+def bake_bytes(N, T, head_on):
+    """Bytes `bake` stores for N Gaussians and T timestamps: a field whose head is on (`head_on[h]`, the order of FIELDS: positions, scales,
+    rotations, opacity, SH) takes one padded slot per timestamp, a field whose head is off one slot in all."""
+    if N < 0 or T < 1 or len(head_on) != len(FIELDS):
+        raise ValueError("bake_bytes: N >= 0, T >= 1 and one flag per field")
+    return 4 * sum(_slot_floats(N, w) * (T if on else 1) for w, on in zip(FIELD_WIDTH, head_on))
+
+
+def _checked_times(times):
+    ts = [float(t) for t in times]
+    if not ts:
+        raise ValueError("times: at least one timestamp")
+    if any(math.isnan(t) or math.isinf(t) for t in ts) or any(b <= a for a, b in zip(ts, ts[1:])):
+        raise ValueError("times: a strictly increasing sequence of finite floats")
+    return ts
+
+
+def _locate(ts, t, interp):
+    t = min(max(float(t), ts[0]), ts[-1])
+    j = bisect.bisect_left(ts, t)                  # the first timestamp >= t
+    if ts[j] == t:
+        return j, j, 0.0
+    i = j - 1
+    if interp == "linear":
+        return i, j, (t - ts[i]) / (ts[j] - ts[i])
+    k = i if t - ts[i] <= ts[j] - t else j         # a tie goes to the lower index
+    return k, k, 0.0
+
+
+def locate(times, t, interp="linear"):
+    """Where frame time `t` falls in the strictly increasing `times` (pure Python, float64): (i, j, w) such that the state at t is
+    state_i + w * (state_j - state_i).  t is clamped to [times[0], times[-1]]; t == times[i] gives (i, i, 0.0); interp="linear" gives the
+    bracketing pair and w = (t - t_i) / (t_j - t_i); interp="nearest" gives (k, k, 0.0) for the nearer timestamp, the lower one on a tie."""
+    if interp not in ("linear", "nearest"):
+        raise ValueError(f"interp: 'linear' or 'nearest', not {interp!r}")
+    return _locate(_checked_times(times), t, interp)
+
+
+def to_rgb8(image, mode="trunc"):
+    """float32 [3,H,W] device image -> uint8 [H,W,3] device tensor (fdgs_image_rgb8).  mode "trunc" is the reference's to8b,
+    (255 * clip(x, 0, 1)).astype(uint8); "round" is what torchvision.utils.save_image stores, x * 255 + 0.5 clamped to [0, 255] and
+    truncated.  NaN pixels are unspecified."""
+    if mode not in _lib.RGB8_MODES:
+        raise ValueError(f"mode: 'trunc' or 'round', not {mode!r}")
+    if image.dim() != 3 or image.shape[0] != 3 or image.dtype != torch.float32:
+        raise ValueError("to_rgb8: a float32 [3,H,W] image")
+    if not _deformation._is_hip_device(image.device):
+        raise _lib.FdgsError("to_rgb8 runs on the GPU only")
+    img = image.detach().contiguous()
+    H, W = int(img.shape[1]), int(img.shape[2])
+    out = torch.empty(H, W, 3, dtype=torch.uint8, device=img.device)
+    _lib.check(_lib.lib().fdgs_image_rgb8(_lib.stream_ptr(), H, W, _lib.RGB8_MODES[mode], _lib.ptr(img), _lib.ptr(out)))
+    return out
+
+
+class BakedFrame:
+    """The five arrays of one timestamp, views into the storage of their `Baked`.  The arrays of a head that is off are the SAME tensors in
+    every frame."""
+    __slots__ = FIELDS
+
+    def __init__(self, arrays):
+        for name, a in zip(FIELDS, arrays):
+            setattr(self, name, a)
+
+    def arrays(self):
+        return tuple(getattr(self, name) for name in FIELDS)
+
+
+class Baked:
+    """The deformed, activated state of a model at `times`, resident on the device: positions [N,3], scales [N,3] (exp applied), rotations
+    [N,4] (unit quaternions), opacity [N,1] (sigmoid applied), SH [N,16,3] -- what the no-grad branch of render() hands to the rasterizer.
+
+    A SNAPSHOT: it holds copies, not references.  Training steps, densification, pruning, a reorder or a loaded checkpoint after `bake`
+    leave it stale (it keeps rendering the model as it was); bake again.
+
+    `times`, `frames[k]` (BakedFrame), `head_on`, `N`, `nbytes` (the stored size, == bake_bytes(N, len(times), head_on); the scratch state
+    of the temporal blend, one more timestamp's worth of the time-dependent fields, is allocated on the first blended frame and not
+    counted), `perm` (the implicit Hilbert permutation the rows are stored in, or None: rows in the model's order)."""
+
+    def __init__(self, times, frames, head_on, perm, storage, active_sh_degree):
+        self.times, self.frames, self.head_on, self.perm = tuple(times), frames, tuple(head_on), perm
+        self._storage = storage
+        self.active_sh_degree = active_sh_degree
+        self.N = int(frames[0].xyz.shape[0])
+        self.nbytes = storage.numel() * storage.element_size()
+        self._scratch = None
+
+    @property
+    def device(self):
+        return self._storage.device
+
+    def blend(self, i, j, w):
+        """The state at weight `w` between frames i and j as a BakedFrame: ONE fdgs_state_blend launch into this object's scratch state
+        (time-dependent fields only; the others are the stored arrays themselves).  The result is overwritten by the next blend."""
+        if self._scratch is None:
+            dev = self.device
+            buf = torch.empty(sum(_slot_floats(self.N, wd) for wd, on in zip(FIELD_WIDTH, self.head_on) if on), dtype=torch.float32, device=dev)
+            arrays, off = [], 0
+            for wd, shp, on, static in zip(FIELD_WIDTH, FIELD_SHAPE, self.head_on, self.frames[0].arrays()):
+                if on:
+                    arrays.append(buf[off:off + self.N * wd].view(self.N, *shp))
+                    off += _slot_floats(self.N, wd)
+                else:
+                    arrays.append(static)
+            self._scratch = (buf, BakedFrame(arrays))
+        out = self._scratch[1]
+        a, b = self.frames[i], self.frames[j]
+        streams = (_lib.BlendStream * _lib.MAX_BLEND_STREAMS)()
+        ns = 0
+        for h, name in enumerate(FIELDS):
+            if self.head_on[h] and name != "rotations":
+                s = streams[ns]
+                s.a, s.b, s.out = getattr(a, name).data_ptr(), getattr(b, name).data_ptr(), getattr(out, name).data_ptr()
+                s.n_floats = self.N * FIELD_WIDTH[h]
+                ns += 1
+        rot = (a.rotations, b.rotations, out.rotations) if self.head_on[2] else (None, None, None)
+        _lib.check(_lib.lib().fdgs_state_blend(_lib.stream_ptr(), float(w), ns, streams, self.N, *[_lib.ptr(r) for r in rot]))
+        return out
+
+    def state_at(self, t, interp="linear"):
+        """(BakedFrame, (i, j, w)) for frame time t: a stored frame when t is a baked timestamp (or interp="nearest"), else the blend."""
+        if interp not in ("linear", "nearest"):
+            raise ValueError(f"interp: 'linear' or 'nearest', not {interp!r}")
+        i, j, w = _locate(self.times, t, interp)
+        if i == j or not any(self.head_on):
+            return self.frames[i], (i, j, w)
+        return self.blend(i, j, w), (i, j, w)
+
+    def render(self, viewpoint_camera, pipe, bg_color, scaling_modifier=1.0, override_color=None, cam_type=None, interp="linear", rgb8=None):
+        """`fdgs.render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, "fine", cam_type)` under torch.no_grad(),
+        with the deformation replaced by the baked state at the camera's time: the same raster settings (the PanopticSports dict camera
+        included), the same result dict -- "viewspace_points" is None (nothing here takes a gradient), "radii" / "visibility_filter" are in
+        the model's row order.  interp: what a time between two baked timestamps gets ("linear" | "nearest").  rgb8 = "trunc" | "round" adds
+        "rgb8", the uint8 [H,W,3] image of to_rgb8.  The pipe's python SH / covariance paths are not available from a baked state."""
+        if pipe.compute_cov3D_python or pipe.convert_SHs_python:
+            raise NotImplementedError("Baked.render: pipe.compute_cov3D_python / pipe.convert_SHs_python need the live model; use fdgs.render")
+        with torch.no_grad():
+            device = self.device
+            _dev = _renderer._dev
+            if cam_type != "PanopticSports":
+                raster_settings = GaussianRasterizationSettings(
+                    image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
+                    tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5), bg=bg_color,
+                    scale_modifier=scaling_modifier, viewmatrix=_dev(viewpoint_camera.world_view_transform, device),
+                    projmatrix=_dev(viewpoint_camera.full_proj_transform, device), sh_degree=self.active_sh_degree,
+                    campos=_dev(viewpoint_camera.camera_center, device), prefiltered=False, debug=pipe.debug)
+                frame_time = float(viewpoint_camera.time)
+            else:
+                raster_settings = viewpoint_camera["camera"]
+                frame_time = float(viewpoint_camera["time"])
+            st, _ = self.state_at(frame_time, interp)
+            shs, colors = st.shs, None
+            if override_color is not None:
+                shs, colors = None, override_color.detach()
+                if self.perm is not None:
+                    colors, = _deformation.permute_rows(self.perm, [colors.float()])
+            image, radii, depth, rstate = _rasterizer.rasterize_forward(raster_settings, st.xyz, shs, colors, st.opacity, st.scales, st.rotations,
+                                                                        None, expect_backward=False)
+            vis = rstate.visibility
+            if self.perm is not None:
+                radii, = _deformation.permute_rows(self.perm, [radii], scatter=True)
+                vis = radii > 0
+            out = {"render": image, "viewspace_points": None, "visibility_filter": vis, "radii": radii, "depth": depth}
+            if rgb8 is not None:
+                out["rgb8"] = to_rgb8(image, rgb8)
+            return out
+
+
+def bake(pc, times, max_bytes=None):
+    """Deforms `pc` once per timestamp and keeps the activated states on the device -> Baked.
+
+    Per time: the deformation.forward_impl(..., activate=True) call of render()'s no-grad branch, on the same inputs -- read through the
+    implicit Hilbert permutation when render() would read them through it (renderer._implicit_perm), so a baked frame rasterizes to the
+    image render() gives, bit for bit.  Arrays of a head that is on are stored per timestamp, arrays of a head that is off once (from the
+    first frame: they do not depend on the time).  Raises ValueError unless `times` is strictly increasing, MemoryError -- before anything
+    is allocated -- when `max_bytes` is given and bake_bytes(...) exceeds it."""
+    ts = _checked_times(times)
+    net = pc._deformation
+    if not isinstance(net, _deformation.deform_network):
+        raise TypeError("bake: pc._deformation must be this package's deform_network")
+    dn = net.deformation_net
+    head_on = _deformation._head_on(dn.args)
+    N, T = int(pc._xyz.shape[0]), len(ts)
+    need = bake_bytes(N, T, head_on)
+    if max_bytes is not None and need > max_bytes:
+        raise MemoryError(f"bake: {T} timestamps of {N} Gaussians need {need} bytes, max_bytes = {max_bytes}")
+    with torch.no_grad():
+        planes, mlp = _deformation._collect(net)
+        cfg = dict(C=dn.grid.grid_config[0]["output_coordinate_dim"], L=len(dn.grid.grids), W=dn.W, head_on=head_on, activate=True,
+                   save=False, grad=False, ordered=_deformation.spatial_order_hint(pc._xyz))
+        perm = _renderer._implicit_perm(pc, cfg, dn)
+        ins = [t.detach() for t in (pc.get_xyz, pc._scaling, pc._rotation, pc._opacity, pc._features_dc, pc._features_rest)]
+        if perm is not None:
+            cfg["ordered"] = True
+            ins = _deformation.permute_rows(perm, ins)
+        storage = torch.empty(need // 4, dtype=torch.float32, device=pc._xyz.device)
+        slots, off = [], 0          # per field: the [N, ...] view of every timestamp (one shared view when the head is off)
+        for w, shp, on in zip(FIELD_WIDTH, FIELD_SHAPE, head_on):
+            stride = _slot_floats(N, w)
+            views = [storage[off + k * stride:off + k * stride + N * w].view(N, *shp) for k in range(T if on else 1)]
+            slots.append(views if on else views * T)
+            off += stride * (T if on else 1)
+        for k, t in enumerate(ts):
+            st = _deformation.forward_impl(cfg, t, *ins, None, dn.grid.aabb, (*planes, *mlp), False)
+            for h, o in enumerate((st.o_xyz, st.o_sc, st.o_rot, st.o_op, st.o_sh)):
+                if head_on[h] or k == 0:
+                    slots[h][k].copy_(o)
+        frames = [BakedFrame([slots[h][k] for h in range(len(FIELDS))]) for k in range(T)]
+    return Baked(ts, frames, head_on, perm, storage, pc.active_sh_degree)
+
+
+def pack_ply_rows(xyz, scales, rotations, opacity, shs):
+    """The float32 [N,62] vertex table of io.write_ply_vertices from raw per-Gaussian arrays on the device (fdgs_pack_ply_rows):
+    columns in the order of io.construct_list_of_attributes, SH coefficients channel-major as GaussianModel.save_ply stores them."""
+    N = int(xyz.shape[0])
+    c = lambda t, w: t.detach().float().contiguous().reshape(N, w)
+    xyz, scales, rotations, opacity, shs = c(xyz, 3), c(scales, 3), c(rotations, 4), c(opacity, 1), c(shs, 48)
+    if not _deformation._is_hip_device(xyz.device):
+        raise _lib.FdgsError("pack_ply_rows runs on the GPU only")
+    out = torch.empty(N, 62, dtype=torch.float32, device=xyz.device)
+    _lib.check(_lib.lib().fdgs_pack_ply_rows(_lib.stream_ptr(), N, *[_lib.ptr(t) for t in (xyz, scales, rotations, opacity, shs, out)]))
+    return out
+
+
+def export_ply_sequence(pc, times, out_dir, pattern="time_{:05d}.ply"):
+    """One static 3DGS point cloud per time, as export_perframe_3DGS.py writes them (gaussian_pertimestamp/time_00000.ply ...): the raw
+    deformation outputs (deform(..., activate=False)) in GaussianModel.save_ply's format, rows in the model's order.  Per time: one
+    deformation forward, one fdgs_pack_ply_rows launch, one device-to-host copy, one file.  Returns the paths."""
+    if pc._features_dc.shape[1] != 1 or pc._features_rest.shape[1] != 15:
+        raise ValueError("export_ply_sequence: SH degree 3 (16 coefficients), what the deformation's SH head produces")
+    names = _io.construct_list_of_attributes(pc)
+    paths = []
+    with torch.no_grad():
+        for k, t in enumerate(times):
+            xyz, sc, rot, op, shs = _deformation.deform(pc._deformation, pc.get_xyz, pc._scaling, pc._rotation, pc._opacity,
+                                                        shs_dc=pc._features_dc, shs_rest=pc._features_rest, time=float(t), activate=False)
+            table = pack_ply_rows(xyz, sc, rot, op, shs).cpu().numpy()
+            path = os.path.join(out_dir, pattern.format(k))
+            _io.write_ply_vertices(path, names, table)
+            paths.append(path)
+    return paths

@@ -477,6 +477,46 @@ int fdgs_spatial_order(void* stream, int N, const float* xyz, const float* bound
 /* the same key function evaluated on the HOST over host arrays (bounds_opt NULL = bounding box): diagnostics / tests, no GPU */
 int fdgs_spatial_keys_host(int N, const float* xyz, const float* bounds_opt, int curve, int bits, uint32_t* keys);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Playback (additions to ABI 6; no existing signature changed): what rendering a trained model from BAKED states needs beside the
+ * rasterizer (csrc/playback.hip).  A baked state is what fdgs_deform_fwd wrote with activate = 1 for one frame time; it depends on the
+ * time only, never on the camera, so a sequence is deformed once per timestamp and every later frame is stages 1-4 alone (fdgs.playback).
+ * The arithmetic of each operation is one host/device function (csrc/playback_ops.h) compiled without contraction, with IEEE `/` and
+ * sqrt: every *_host twin below returns, over host arrays and without a GPU, bit for bit what the device entry point writes.
+ * All launches go on `stream`; nothing synchronises.  Bad arguments return FDGS_E_INVALID with a message before anything is launched.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* Temporal blend of two baked states at weight w in [0, 1] (w = 0: state a), ONE launch for all of it:
+ *   flat streams (positions, scales, opacities, SH coefficients; any subset):   out = a + w * (b - a)          element-wise, three roundings
+ *   rotations [N,4], unit quaternions in, unit quaternions out (rot_* all NULL: none):
+ *        s = dot(a, b) < 0 ? -1 : 1;  q = a + w * (s * b - a);  out = q / max(sqrt(q . q), 1e-12)
+ *        (dot product and squared norm summed in index order 0, 1, 2, 3)
+ *   `streams` is a HOST array; a, b, out of every stream and the rotations are device pointers, 16-byte aligned (a lane moves 16 bytes;
+ *   the n_floats % 4 floats at the end of a stream are handled singly); out overlaps neither a nor b.  A stream with
+ *   n_floats = 0 is skipped; nothing to do (N = 0 and no floats) succeeds without a launch.  The *_host twin takes host pointers of any
+ *   alignment. */
+#define FDGS_MAX_BLEND_STREAMS 4
+typedef struct fdgs_blend_stream { const float* a; const float* b; float* out; size_t n_floats; } fdgs_blend_stream;
+int fdgs_state_blend(void* stream, float w, int nstreams, const fdgs_blend_stream* streams, int N, const float* rot_a,
+                     const float* rot_b, float* rot_out);
+int fdgs_state_blend_host(float w, int nstreams, const fdgs_blend_stream* streams, int N, const float* rot_a,
+                          const float* rot_b, float* rot_out);
+/* The vertex table of a static 3DGS PLY (GaussianModel.save_ply's attribute order) from RAW deformation outputs (activate = 0):
+ *   xyz [N,3], scales [N,3], rotations [N,4], opacity [N,1], shs [N,16,3]  ->  out float32 [N,62]:
+ *   x y z | nx ny nz (zeros) | f_dc_c = shs[n,0,c] | f_rest_{c * 15 + k} = shs[n,1+k,c] | opacity | scale_0..2 | rot_0..3
+ * Pure data movement.  N = 0 succeeds and writes nothing. */
+int fdgs_pack_ply_rows(void* stream, int N, const float* xyz, const float* scales, const float* rotations, const float* opacity,
+                       const float* shs, float* out);
+int fdgs_pack_ply_rows_host(int N, const float* xyz, const float* scales, const float* rotations, const float* opacity,
+                            const float* shs, float* out);
+/* float32 image [3,H,W] -> uint8 [H,W,3]:
+ *   FDGS_RGB8_TRUNC  (uint8)(255.f * min(max(x, 0), 1))                              one rounding, then truncation (the reference's to8b)
+ *   FDGS_RGB8_ROUND  t = x * 255.f; t = t + 0.5f; clamp to [0, 255]; truncate        two roundings (torchvision.utils.save_image)
+ * The result for a NaN input is unspecified in both modes.  An empty image succeeds and writes nothing. */
+#define FDGS_RGB8_TRUNC 0
+#define FDGS_RGB8_ROUND 1
+int fdgs_image_rgb8(void* stream, int H, int W, int mode, const float* image, uint8_t* out);
+int fdgs_image_rgb8_host(int H, int W, int mode, const float* image, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif
