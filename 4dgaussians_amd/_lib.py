@@ -98,6 +98,16 @@ class BlendStream(Structure):
 
 MAX_BLEND_STREAMS = 4
 
+
+class Placement(Structure):
+    _fields_ = [("scale", c_float), ("rot", c_float * 9), ("quat", c_float * 4), ("shift", c_float * 3), ("sh1", c_float * 9),
+                ("sh2", c_float * 25), ("sh3", c_float * 49), ("mode", c_int), ("sh_degree", c_int)]
+
+
+class StateArrays(Structure):
+    _fields_ = [("xyz", c_void_p), ("scales", c_void_p), ("rotations", c_void_p), ("opacity", c_void_p), ("shs", c_void_p)]
+
+
 # every symbol include/fdgs.h declares: (restype, argtypes)
 SYMBOLS = {
     "fdgs_last_error": (c_char_p, []),
@@ -152,9 +162,14 @@ SYMBOLS = {
     "fdgs_pack_ply_rows_host": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdgs_image_rgb8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "fdgs_image_rgb8_host": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p]),
+    "fdgs_state_place": (c_int, [c_void_p, POINTER(Placement), c_int, c_uint32, POINTER(StateArrays), POINTER(StateArrays), c_float,
+                                 POINTER(StateArrays)]),
+    "fdgs_state_place_host": (c_int, [POINTER(Placement), c_int, c_uint32, POINTER(StateArrays), POINTER(StateArrays), c_float,
+                                      POINTER(StateArrays)]),
 }
 CURVES = {"hilbert": 0, "morton": 1}      # FDGS_CURVE_*
 RGB8_MODES = {"trunc": 0, "round": 1}     # FDGS_RGB8_*
+PLACE_MODES = {"points": 0, "rigid": 1}   # FDGS_PLACE_*
 
 ABI_VERSION = 6       # what this Python host was written against (include/fdgs.h); checked when the library is loaded
 

@@ -1,0 +1,326 @@
+"""Scene composition: several baked 4D models placed in one frame and rasterized once.
+
+The reference's merge_many_4dgs.py deforms every model at the frame's time, moves each added model with a shift, a rotation and a scale,
+concatenates all fields and rasterizes.  Here the models are `playback.Baked` states that stay in device memory, every model owns a fixed
+range of rows of ONE composite state, and a frame is one fdgs_state_place launch per model whose time bracket changed -- the temporal
+blend of the two bracketing baked frames fused into it -- followed by the rasterizer:
+
+    scene = fdgs.compose.compose([baked_a, baked_b], [None, fdgs.compose.Placement(rotation=R, translation=d, scale=s)])
+    for cam in cameras:
+        out = scene.render(cam, pipe, background)               # the contract of Baked.render
+
+A placement is a similarity transform (scale, then rotation, then shift -- the script's order).  mode="rigid" (the default) turns the
+orientations of the splats and their view-dependent colour with the model: the placed model looks exactly like the model seen from the
+inversely moved camera.  mode="points" is the script's own behaviour (`Placement.from_reference`): positions and scales only, so a turned
+object keeps its splats and its highlights pointing the old way.  Fields of a model whose deformation head is off do not depend on the time
+and are placed once, in `compose`.  No gradient flows through any of this.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import deformation as _deformation
+from . import rasterizer as _rasterizer
+from . import renderer as _renderer
+from . import sh as _sh
+from .playback import FIELD_SHAPE, FIELD_WIDTH, FIELDS, BakedFrame, _locate, _slot_floats, to_rgb8
+from .rasterizer import GaussianRasterizationSettings
+
+WRAPS = ("clamp", "loop", "pingpong")
+_SH_ZERO = 1e-13        # entries of a band matrix below this are structural zeros of the rotation (the solve leaves ~1e-16 there)
+
+
+def _fit_directions(n=64):
+    """n well-spread unit directions (a Fibonacci spiral on the sphere), float64: the fixed sample sh_rotation fits on."""
+    k = np.arange(n, dtype=np.float64) + 0.5
+    z = 1.0 - 2.0 * k / n
+    phi = k * (math.pi * (3.0 - math.sqrt(5.0)))
+    r = np.sqrt(1.0 - z * z)
+    return np.stack((r * np.cos(phi), r * np.sin(phi), z), axis=1)
+
+
+def _basis64(dirs):
+    """This package's SH basis (sh.basis, degree 3) at float64 directions [n,3] -> [n,16]."""
+    return torch.cat(_sh.basis(3, torch.from_numpy(np.ascontiguousarray(dirs, dtype=np.float64))), dim=-1).numpy()
+
+
+def sh_rotation(R):
+    """(M1 [3,3], M2 [5,5], M3 [7,7]), float64: how the coefficients of SH bands 1 .. 3 mix when the model is turned by the rotation R.
+    For every unit direction and coefficient row c [16]:  eval_sh(3, c @ blockdiag(1, M1, M2, M3), dir) == eval_sh(3, c, R^T dir),
+    i.e. B(dir R) = B(dir) M^T for the basis row B.  Computed from sh.basis itself: the least-squares solution of B(D) X = B(D R) over 64
+    fixed directions D (condition number 2.5), X = M^T; the off-block terms of X are rounding noise and only the diagonal blocks are kept.
+    Entries below 1e-13 in magnitude are structural zeros and are returned as 0, so M(identity) is the identity exactly."""
+    R = np.asarray(R, dtype=np.float64).reshape(3, 3)
+    D = _fit_directions()
+    X = np.linalg.lstsq(_basis64(D), _basis64(D @ R), rcond=None)[0]
+    out = []
+    for l in (1, 2, 3):
+        M = np.ascontiguousarray(X[l * l:(l + 1) ** 2, l * l:(l + 1) ** 2].T)
+        M[np.abs(M) < _SH_ZERO] = 0.0
+        out.append(M)
+    return tuple(out)
+
+
+def _quat_to_matrix(q):
+    r, x, y, z = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y)],
+                     [2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x)],
+                     [2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)]], dtype=np.float64)
+
+
+def _matrix_to_quat(R):
+    """Unit quaternion (r, x, y, z), r >= 0, of a rotation matrix (float64; the branch with the largest pivot)."""
+    t = np.trace(R)
+    if t > 0:
+        s = math.sqrt(t + 1.0) * 2
+        q = (0.25 * s, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s)
+    elif R[0, 0] > R[1, 1] and R[0, 0] > R[2, 2]:
+        s = math.sqrt(1.0 + R[0, 0] - R[1, 1] - R[2, 2]) * 2
+        q = ((R[2, 1] - R[1, 2]) / s, 0.25 * s, (R[0, 1] + R[1, 0]) / s, (R[0, 2] + R[2, 0]) / s)
+    elif R[1, 1] > R[2, 2]:
+        s = math.sqrt(1.0 + R[1, 1] - R[0, 0] - R[2, 2]) * 2
+        q = ((R[0, 2] - R[2, 0]) / s, (R[0, 1] + R[1, 0]) / s, 0.25 * s, (R[1, 2] + R[2, 1]) / s)
+    else:
+        s = math.sqrt(1.0 + R[2, 2] - R[0, 0] - R[1, 1]) * 2
+        q = ((R[1, 0] - R[0, 1]) / s, (R[0, 2] + R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, 0.25 * s)
+    q = np.array(q, dtype=np.float64)
+    q /= np.linalg.norm(q)
+    return -q if q[0] < 0 else q
+
+
+class Placement:
+    """Where one model goes in the composite: x -> scale * x, turned by `rotation`, shifted by `translation`; and how its time runs.
+
+    rotation: a 3x3 matrix (orthonormal, det +1, within 1e-6), a unit quaternion (r, x, y, z) (norm within 1e-6 of 1) or None (identity);
+    scale: positive and finite; mode: "rigid" | "points" (see the module docstring); the model's frame time is
+    map_time(times, t, placement) = wrap(time_scale * t + time_offset).  Anything else raises ValueError.
+
+    The parameters are rounded to float32 ONCE, here; the object exposes what the kernel gets: `scale` (np.float32), `rotation` [3,3],
+    `quat` [4], `translation` [3], `sh` = (M1, M2, M3) of sh_rotation(rotation given), all float32 numpy arrays."""
+
+    def __init__(self, rotation=None, translation=(0.0, 0.0, 0.0), scale=1.0, mode="rigid", time_scale=1.0, time_offset=0.0, wrap="clamp"):
+        if mode not in _lib.PLACE_MODES:
+            raise ValueError(f"mode: 'rigid' or 'points', not {mode!r}")
+        if wrap not in WRAPS:
+            raise ValueError(f"wrap: one of {WRAPS}, not {wrap!r}")
+        s = float(scale)
+        if not (math.isfinite(s) and s > 0 and math.isfinite(float(np.float32(s))) and float(np.float32(s)) > 0):
+            raise ValueError("scale: positive and finite")
+        d = np.asarray(translation, dtype=np.float64).reshape(-1)
+        if d.shape != (3,) or not np.isfinite(d).all():
+            raise ValueError("translation: three finite numbers")
+        if not (math.isfinite(float(time_scale)) and math.isfinite(float(time_offset))):
+            raise ValueError("time_scale, time_offset: finite numbers")
+        if rotation is None:
+            R = np.eye(3)
+        else:
+            r = np.asarray(rotation.detach().cpu().numpy() if isinstance(rotation, torch.Tensor) else rotation, dtype=np.float64)
+            if r.shape == (4,):
+                if not np.isfinite(r).all() or abs(np.linalg.norm(r) - 1.0) > 1e-6:
+                    raise ValueError("rotation: a UNIT quaternion (r, x, y, z)")
+                R = _quat_to_matrix(r / np.linalg.norm(r))
+            elif r.shape == (3, 3):
+                if not np.isfinite(r).all() or np.abs(r @ r.T - np.eye(3)).max() > 1e-6 or abs(np.linalg.det(r) - 1.0) > 1e-6:
+                    raise ValueError("rotation: an orthonormal 3x3 matrix with determinant +1")
+                R = r
+            else:
+                raise ValueError("rotation: a 3x3 matrix, a unit quaternion (r, x, y, z) or None")
+        f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+        self.scale = np.float32(s)
+        self.rotation, self.quat, self.translation = f32(R), f32(_matrix_to_quat(R)), f32(d)
+        self.sh = tuple(f32(M) for M in sh_rotation(R))
+        self.mode, self.wrap = mode, wrap
+        self.time_scale, self.time_offset = float(time_scale), float(time_offset)
+
+    @classmethod
+    def from_reference(cls, motion_bias=(0.0, 0.0, 0.0), rotation_bias=(0.0, 0.0), scales_bias=1.0):
+        """The arguments merge_many_4dgs.py takes for one added model: rotate_point_cloud(p, motion_bias, (theta, phi), scales_bias) =
+        (p * scales_bias) @ (Rz(theta) Rx(phi))^T + motion_bias and scales * scales_bias, orientations and SH untouched (mode="points")."""
+        theta, phi = (float(v) for v in rotation_bias)
+        Rz = np.array([[math.cos(theta), -math.sin(theta), 0.0], [math.sin(theta), math.cos(theta), 0.0], [0.0, 0.0, 1.0]])
+        Rx = np.array([[1.0, 0.0, 0.0], [0.0, math.cos(phi), -math.sin(phi)], [0.0, math.sin(phi), math.cos(phi)]])
+        return cls(rotation=Rz @ Rx, translation=[float(v) for v in motion_bias], scale=float(scales_bias), mode="points")
+
+    def struct(self, sh_degree):
+        """The fdgs_placement of this placement for a model of active SH degree `sh_degree`."""
+        p = _lib.Placement()
+        p.scale = float(self.scale)
+        p.rot[:] = self.rotation.reshape(-1).tolist()
+        p.quat[:] = self.quat.tolist()
+        p.shift[:] = self.translation.tolist()
+        p.sh1[:] = self.sh[0].reshape(-1).tolist()
+        p.sh2[:] = self.sh[1].reshape(-1).tolist()
+        p.sh3[:] = self.sh[2].reshape(-1).tolist()
+        p.mode, p.sh_degree = _lib.PLACE_MODES[self.mode], int(sh_degree)
+        return p
+
+
+def map_time(times, t, placement):
+    """The time a model with baked `times` is shown at when the composite's frame time is t (pure Python, float64):
+    t' = placement.time_scale * t + placement.time_offset, wrapped onto [times[0], times[-1]].  A t' inside the range (both ends
+    included) is returned as it is; outside, "clamp" takes the nearer end, "loop" repeats the range (t' modulo the span), "pingpong"
+    runs it forwards and backwards.  A single timestamp maps to itself."""
+    lo, hi = float(times[0]), float(times[-1])
+    tp = placement.time_scale * float(t) + placement.time_offset
+    span = hi - lo
+    if span <= 0.0:
+        return lo
+    if lo <= tp <= hi:
+        return tp
+    if placement.wrap == "clamp" or not math.isfinite(tp):
+        return lo if tp < lo else hi
+    if placement.wrap == "loop":
+        return lo + (tp - lo) % span
+    x = (tp - lo) % (2.0 * span)
+    return lo + (x if x <= span else 2.0 * span - x)
+
+
+def compose_bytes(Ns):
+    """Bytes `compose` stores for models of Ns[m] Gaussians: one placed state of sum(Ns) rows, each of its five arrays padded to
+    playback.SLOT_ALIGN_FLOATS."""
+    Ns = [int(n) for n in Ns]
+    if not Ns or any(n < 0 for n in Ns):
+        raise ValueError("compose_bytes: at least one model, N >= 0")
+    total = sum(Ns)
+    return 4 * sum(_slot_floats(total, w) for w in FIELD_WIDTH)
+
+
+class Composite:
+    """Several baked models in one world, as ONE placed state of sum(N) rows resident on the device.
+
+    A SNAPSHOT like `Baked`: it refers to the baked frames of its models and holds placed copies.  Baking a model again, or changing a
+    placement object afterwards, leaves it stale; compose again.
+
+    `models`, `placements`, `N` (all rows), `offsets[m]` / `slices[m]` (model m's rows: [offset_m, offset_m + N_m), in that model's own row
+    order for everything `render` returns), `nbytes` (== compose_bytes(Ns)), `active_sh_degree` (the maximum over the models; the bands a
+    model does not have are stored as zeros), `launches` (fdgs_state_place launches so far, the static fields' in compose() included)."""
+
+    def __init__(self, models, placements, storage, arrays):
+        self.models, self.placements = tuple(models), tuple(placements)
+        self._storage, self._arrays = storage, arrays
+        self.N = int(arrays[0].shape[0])
+        self.offsets, off = [], 0
+        for m in self.models:
+            self.offsets.append(off)
+            off += m.N
+        self.offsets = tuple(self.offsets)
+        self.slices = tuple(slice(o, o + m.N) for o, m in zip(self.offsets, self.models))
+        self.nbytes = storage.numel() * storage.element_size()
+        self.active_sh_degree = max(m.active_sh_degree for m in self.models)
+        self.launches = 0
+        self._structs = [p.struct(m.active_sh_degree) for p, m in zip(self.placements, self.models)]
+        self._shown = [None] * len(self.models)          # per model: the (i, j, w) its time-dependent rows hold
+        self._frame = BakedFrame(arrays)
+
+    @property
+    def device(self):
+        return self._storage.device
+
+    def _place(self, m, mask, i, j, w):
+        model = self.models[m]
+        if mask == 0 or model.N == 0:
+            return
+        a, b, out = _lib.StateArrays(), _lib.StateArrays(), _lib.StateArrays()
+        fa, fb = model.frames[i], model.frames[j]
+        for h, name in enumerate(FIELDS):
+            if mask >> h & 1:
+                setattr(a, name, getattr(fa, name).data_ptr())
+                setattr(b, name, getattr(fb, name).data_ptr())
+                setattr(out, name, self._arrays[h].data_ptr() + 4 * self.offsets[m] * FIELD_WIDTH[h])
+        blend = i != j
+        _lib.check(_lib.lib().fdgs_state_place(_lib.stream_ptr(), self._structs[m], model.N, mask, a, b if blend else None,
+                                               float(w) if blend else 0.0, out))
+        self.launches += 1
+
+    def state_at(self, t, interp="linear"):
+        """The composite state at frame time t as a BakedFrame over this object's arrays (overwritten by the next call): per model, ONE
+        fdgs_state_place launch for its time-dependent fields, straight from the two baked frames that bracket map_time(times, t,
+        placement) with the blend fused -- or no launch when that model's (i, j, w) is what its rows already hold."""
+        if interp not in ("linear", "nearest"):
+            raise ValueError(f"interp: 'linear' or 'nearest', not {interp!r}")
+        for m, (model, pl) in enumerate(zip(self.models, self.placements)):
+            mask = sum(1 << h for h, on in enumerate(model.head_on) if on)
+            if mask == 0:
+                continue
+            key = _locate(model.times, map_time(model.times, t, pl), interp)
+            if key != self._shown[m]:
+                self._place(m, mask, *key)
+                self._shown[m] = key
+        return self._frame
+
+    def render(self, viewpoint_camera, pipe, bg_color, scaling_modifier=1.0, override_color=None, cam_type=None, interp="linear", rgb8=None):
+        """The contract of `Baked.render` for the whole scene: the same raster settings (the PanopticSports dict camera included), the same
+        result dict.  "radii" / "visibility_filter" have sum(N) entries, model m's at `slices[m]` in that model's own row order (segments
+        of models stored through a permutation are scattered back); `override_color` is [sum(N), 3] in the same order."""
+        if pipe.compute_cov3D_python or pipe.convert_SHs_python:
+            raise NotImplementedError("Composite.render: pipe.compute_cov3D_python / pipe.convert_SHs_python need the live model; use fdgs.render")
+        with torch.no_grad():
+            device = self.device
+            _dev = _renderer._dev
+            if cam_type != "PanopticSports":
+                raster_settings = GaussianRasterizationSettings(
+                    image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
+                    tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5), bg=bg_color,
+                    scale_modifier=scaling_modifier, viewmatrix=_dev(viewpoint_camera.world_view_transform, device),
+                    projmatrix=_dev(viewpoint_camera.full_proj_transform, device), sh_degree=self.active_sh_degree,
+                    campos=_dev(viewpoint_camera.camera_center, device), prefiltered=False, debug=pipe.debug)
+                frame_time = float(viewpoint_camera.time)
+            else:
+                raster_settings = viewpoint_camera["camera"]
+                frame_time = float(viewpoint_camera["time"])
+            st = self.state_at(frame_time, interp)
+            permuted = any(m.perm is not None for m in self.models)
+            shs, colors = st.shs, None
+            if override_color is not None:
+                shs, colors = None, override_color.detach().float()
+                if permuted:
+                    colors = torch.cat([c if m.perm is None else _deformation.permute_rows(m.perm, [c.contiguous()])[0]
+                                        for m, c in ((m, colors[sl]) for m, sl in zip(self.models, self.slices))])
+            image, radii, depth, rstate = _rasterizer.rasterize_forward(raster_settings, st.xyz, shs, colors, st.opacity, st.scales, st.rotations,
+                                                                        None, expect_backward=False)
+            vis = rstate.visibility
+            if permuted:
+                radii = torch.cat([r if m.perm is None else _deformation.permute_rows(m.perm, [r.contiguous()], scatter=True)[0]
+                                   for m, r in ((m, radii[sl]) for m, sl in zip(self.models, self.slices))])
+                vis = radii > 0
+            out = {"render": image, "viewspace_points": None, "visibility_filter": vis, "radii": radii, "depth": depth}
+            if rgb8 is not None:
+                out["rgb8"] = to_rgb8(image, rgb8)
+            return out
+
+
+def compose(models, placements=None, max_bytes=None):
+    """Places `models` (a sequence of playback.Baked) in one world -> Composite.  placements[m] is a Placement or None (the identity);
+    placements=None leaves every model where it is.  The composite owns ONE placed state of sum(N) rows: five arrays, each starting on a
+    playback.SLOT_ALIGN_FLOATS boundary, model m in rows [offset_m, offset_m + N_m).  Fields whose head is off in a model do not depend on
+    the time and are placed here, once; the others per frame (Composite.state_at).  Raises ValueError for models on different devices,
+    MemoryError -- before anything is allocated -- when `max_bytes` is given and compose_bytes(...) exceeds it."""
+    models = list(models)
+    if not models:
+        raise ValueError("compose: at least one model")
+    if placements is None:
+        placements = [None] * len(models)
+    placements = [Placement() if p is None else p for p in placements]
+    if len(placements) != len(models) or not all(isinstance(p, Placement) for p in placements):
+        raise ValueError("compose: one Placement (or None) per model")
+    device = models[0].device
+    if any(m.device != device for m in models):
+        raise ValueError("compose: every model must be on the same device")
+    need = compose_bytes([m.N for m in models])
+    if max_bytes is not None and need > max_bytes:
+        raise MemoryError(f"compose: {sum(m.N for m in models)} Gaussians need {need} bytes, max_bytes = {max_bytes}")
+    if not _deformation._is_hip_device(device):
+        raise _lib.FdgsError("compose runs on the GPU only")
+    total = sum(m.N for m in models)
+    with torch.no_grad():
+        storage = torch.empty(need // 4, dtype=torch.float32, device=device)
+        arrays, off = [], 0
+        for w, shp in zip(FIELD_WIDTH, FIELD_SHAPE):
+            arrays.append(storage[off:off + total * w].view(total, *shp))
+            off += _slot_floats(total, w)
+        scene = Composite(models, placements, storage, arrays)
+        for m, model in enumerate(models):
+            scene._place(m, sum(1 << h for h, on in enumerate(model.head_on) if not on), 0, 0, 0.0)
+    return scene

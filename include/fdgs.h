@@ -517,6 +517,48 @@ int fdgs_pack_ply_rows_host(int N, const float* xyz, const float* scales, const 
 int fdgs_image_rgb8(void* stream, int H, int W, int mode, const float* image, uint8_t* out);
 int fdgs_image_rgb8_host(int H, int W, int mode, const float* image, uint8_t* out);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Scene composition (additions to ABI 6; no existing signature changed): several baked models in one frame (csrc/compose.hip,
+ * fdgs.compose).  Each model is moved into a common world by a PLACEMENT, a similarity transform, and written into its rows of one
+ * composite state that is rasterized once -- what the reference's merge_many_4dgs.py does with torch ops and a `cat` per frame.
+ * The arithmetic is one host/device function per operation (csrc/compose_ops.h, contraction off, `*` `+` `-` only): the *_host twin
+ * returns bit for bit what the device writes.
+ *
+ *   scale       s > 0, finite
+ *   rot         R, row-major 3x3, orthonormal, det +1;   quat = the unit quaternion of R in the rasterizer's (r, x, y, z) order
+ *   shift       d
+ *   sh1 sh2 sh3 M1 [3x3], M2 [5x5], M3 [7x7], row-major [j][k]: how the coefficients of SH band l mix under R (fdgs.compose.sh_rotation)
+ *   mode        FDGS_PLACE_POINTS  the reference script: positions and scales are placed, rotations and SH are copied bit for bit
+ *               FDGS_PLACE_RIGID   rotations and SH are turned as well: the placed model looks like the model seen from the moved camera
+ *   sh_degree   the model's active SH degree, 0 .. 3
+ *
+ *   positions   t_k = s * p_k;  y_i = R[i][0] * t_0 + R[i][1] * t_1 + R[i][2] * t_2 (left to right);  out_i = y_i + d_i
+ *   scales      out_k = s * scale_k                             (activated scales are lengths)
+ *   rotations   RIGID: out = quat (x) q, the Hamilton product, every component four products summed as csrc/compose_ops.h writes them;
+ *               not renormalised
+ *   opacity     a copy, always
+ *   SH [16,3]   per colour channel: band 0 is copied; RIGID: band l = 1 .. 3, out[k] = sum_j in[j] * M_l[j][k], j ascending from +0;
+ *               in both modes the bands above sh_degree are written as +0.0 (a model of lower degree is exact inside a composite of a
+ *               higher one)
+ *
+ * When a second state b is given every value is first blended at weight w in [0, 1] exactly as fdgs_state_blend blends it (the same
+ * functions), then placed: the result is fdgs_state_blend followed by a placement, bit for bit, in one launch.  b == NULL: no blend,
+ * w must be 0.
+ *
+ * Bit h of field_mask selects field h in the order of fdgs_state_arrays (positions, scales, rotations, opacity, SH); a field that is not
+ * selected is neither read nor written and its pointers may be NULL.  a (and b) are the arrays of a baked state: device pointers, the
+ * rotations and SH 16-byte aligned.  `out` points at the destination of row 0 of THIS model inside the composite, already offset by the
+ * caller: 4-byte alignment is all it needs.  out overlaps neither a nor b.  N = 0 or field_mask = 0 succeed without a launch; otherwise
+ * ONE launch on `stream`, the placement passed by value.  The *_host twin takes host pointers of any alignment. */
+#define FDGS_PLACE_POINTS 0
+#define FDGS_PLACE_RIGID 1
+typedef struct fdgs_placement { float scale; float rot[9]; float quat[4]; float shift[3]; float sh1[9]; float sh2[25]; float sh3[49]; int mode; int sh_degree; } fdgs_placement;
+typedef struct fdgs_state_arrays { float *xyz, *scales, *rotations, *opacity, *shs; } fdgs_state_arrays;
+int fdgs_state_place(void* stream, const fdgs_placement* p, int N, unsigned field_mask, const fdgs_state_arrays* a,
+                     const fdgs_state_arrays* b, float w, const fdgs_state_arrays* out);
+int fdgs_state_place_host(const fdgs_placement* p, int N, unsigned field_mask, const fdgs_state_arrays* a,
+                          const fdgs_state_arrays* b, float w, const fdgs_state_arrays* out);
+
 #ifdef __cplusplus
 }
 #endif
