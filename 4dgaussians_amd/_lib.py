@@ -166,6 +166,14 @@ SYMBOLS = {
                                  POINTER(StateArrays)]),
     "fdgs_state_place_host": (c_int, [POINTER(Placement), c_int, c_uint32, POINTER(StateArrays), POINTER(StateArrays), c_float,
                                       POINTER(StateArrays)]),
+    "fdgs_state_extent": (c_int, [c_void_p, c_int, c_uint32, POINTER(StateArrays), POINTER(StateArrays), c_void_p]),
+    "fdgs_state_extent_host": (c_int, [c_int, c_uint32, POINTER(StateArrays), POINTER(StateArrays), c_void_p]),
+    "fdgs_state_gather": (c_int, [c_void_p, c_int, c_void_p, c_int, c_uint32, POINTER(StateArrays), POINTER(StateArrays)]),
+    "fdgs_state_gather_host": (c_int, [c_int, c_void_p, c_int, c_uint32, POINTER(StateArrays), POINTER(StateArrays)]),
+    "fdgs_state_scatter": (c_int, [c_void_p, c_int, c_void_p, c_int, c_uint32, POINTER(StateArrays), POINTER(StateArrays), c_float,
+                                   POINTER(StateArrays)]),
+    "fdgs_state_scatter_host": (c_int, [c_int, c_void_p, c_int, c_uint32, POINTER(StateArrays), POINTER(StateArrays), c_float,
+                                        POINTER(StateArrays)]),
 }
 CURVES = {"hilbert": 0, "morton": 1}      # FDGS_CURVE_*
 RGB8_MODES = {"trunc": 0, "round": 1}     # FDGS_RGB8_*

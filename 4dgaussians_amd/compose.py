@@ -25,7 +25,7 @@ from . import deformation as _deformation
 from . import rasterizer as _rasterizer
 from . import renderer as _renderer
 from . import sh as _sh
-from .playback import FIELD_SHAPE, FIELD_WIDTH, FIELDS, BakedFrame, _locate, _slot_floats, to_rgb8
+from .playback import FIELD_SHAPE, FIELD_WIDTH, FIELDS, BakedFrame, SparseBaked, _locate, _slot_floats, to_rgb8
 from .rasterizer import GaussianRasterizationSettings
 
 WRAPS = ("clamp", "loop", "pingpong")
@@ -295,7 +295,8 @@ def compose(models, placements=None, max_bytes=None):
     """Places `models` (a sequence of playback.Baked) in one world -> Composite.  placements[m] is a Placement or None (the identity);
     placements=None leaves every model where it is.  The composite owns ONE placed state of sum(N) rows: five arrays, each starting on a
     playback.SLOT_ALIGN_FLOATS boundary, model m in rows [offset_m, offset_m + N_m).  Fields whose head is off in a model do not depend on
-    the time and are placed here, once; the others per frame (Composite.state_at).  Raises ValueError for models on different devices,
+    the time and are placed here, once; the others per frame (Composite.state_at).  Raises TypeError for a model that is not a Baked (a
+    playback.SparseBaked has no per-timestamp frames to place), ValueError for models on different devices,
     MemoryError -- before anything is allocated -- when `max_bytes` is given and compose_bytes(...) exceeds it."""
     models = list(models)
     if not models:
@@ -305,6 +306,10 @@ def compose(models, placements=None, max_bytes=None):
     placements = [Placement() if p is None else p for p in placements]
     if len(placements) != len(models) or not all(isinstance(p, Placement) for p in placements):
         raise ValueError("compose: one Placement (or None) per model")
+    for m in models:
+        if isinstance(m, SparseBaked) or not hasattr(m, "frames"):
+            raise TypeError(f"compose: a model must be a playback.Baked (dense per-timestamp frames), not {type(m).__name__}; "
+                            "composites of sparse bakes are not supported")
     device = models[0].device
     if any(m.device != device for m in models):
         raise ValueError("compose: every model must be on the same device")

@@ -8,6 +8,8 @@
 //   blend_lerp   out = a + w * (b - a)                                                     three roundings
 //   blend_quat   s = dot(a, b) < 0 ? -1 : 1;  q = a + w * (s * b - a);  out = q / max(sqrt(q . q), 1e-12)
 //                dot product and squared norm summed in index order 0, 1, 2, 3 (s * b is exact)
+//   extent_step  e = max(e, |cur - ref|), +inf when the difference is a NaN               (fdgs_state_extent; fdgs_state_scatter blends
+//                                                                                          with blend_lerp / blend_quat, fdgs_state_gather copies)
 //   ply_source   which input float lands in column c of a row of io.write_ply_vertices' table (pure data movement)
 //   rgb8_value   mode 0: (uint8)(255.f * min(max(x, 0), 1))           the reference's to8b: one rounding, truncation
 //                mode 1: t = x * 255.f; t = t + 0.5f; clamp to [0, 255]; truncate        torchvision.utils.save_image: two roundings
@@ -57,7 +59,22 @@ FDGS_HD inline void blend_quat(const float* a, const float* b, float w, float* o
     for (int k = 0; k < 4; k++) out[k] = q[k] / len;
 }
 
-constexpr int PLY_COLUMNS = 62;      // x y z | nx ny nz | f_dc_0..2 | f_rest_0..44 | opacity | scale_0..2 | rot_0..3
+// one component of fdgs_state_extent: the running maximum e after |cur - ref|; a NaN difference makes it +inf.  The result of a whole row
+// does not depend on the order of its components (a maximum; +inf absorbs), so lanes may each fold a part from +0 and the parts be
+// folded into e by extent_merge: the bits are those of the sequential loop (for every e that is not itself a NaN; the caller zero-fills
+// the array and nothing here ever writes one).
+FDGS_HD inline float extent_step(float e, float cur, float ref) {
+#pragma clang fp contract(off)
+    const float d = cur - ref;
+    const float m = fabsf(d);
+    if (m != m) return INFINITY;
+    return m > e ? m : e;
+}
+
+// e after a partial maximum m (never NaN: it came from extent_step started at +0)
+FDGS_HD inline float extent_merge(float e, float m) { return m > e ? m : e; }
+
+constexpr int PLY_COLUMNS = 62;     // x y z | nx ny nz | f_dc_0..2 | f_rest_0..44 | opacity | scale_0..2 | rot_0..3
 
 // column c (0 .. 61) of row n of the vertex table: *array = 0 xyz, 1 scales, 2 rotations, 3 opacity, 4 shs, -1 the constant zero (normals);
 // returns the float index inside that array.  f_rest_{ch * 15 + k} = shs[n, 1 + k, ch]: the reference's transpose(1, 2).flatten(start_dim=1).

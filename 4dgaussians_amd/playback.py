@@ -17,6 +17,11 @@ for the quaternions) or the nearer baked frame (`interp="nearest"`).  At a baked
 Memory: 236 bytes per Gaussian and timestamp with all five heads on (59 floats), 40 bytes with the dnerf / hypernerf defaults (no_do,
 no_dshs: opacity and SH do not change with time and are stored once); `bake_bytes` is the exact figure, `bake(..., max_bytes=)` refuses
 before it allocates.
+
+Where much of the set hardly moves, `bake_sparse(gaussians, times, tol)` keeps ONE full state and per timestamp only the rows whose baked
+values leave a tolerance band around their values at times[0]; `motion_extent` reports per row how far they go, `sparse_bake_bytes` is
+the exact stored size.  `SparseBaked.render` has the contract of `Baked.render`; a frame at a new time is one fdgs_state_scatter launch
+over the dynamic rows.
 """
 import bisect
 import math
@@ -111,6 +116,43 @@ class BakedFrame:
         return tuple(getattr(self, name) for name in FIELDS)
 
 
+def _render_state(model, who, viewpoint_camera, pipe, bg_color, scaling_modifier, override_color, cam_type, interp, rgb8):
+    """The body of Baked.render and SparseBaked.render: the rasterizer on `model.state_at(frame time, interp)`.  `model` has `device`,
+    `perm`, `active_sh_degree` and `state_at`."""
+    if pipe.compute_cov3D_python or pipe.convert_SHs_python:
+        raise NotImplementedError(f"{who}: pipe.compute_cov3D_python / pipe.convert_SHs_python need the live model; use fdgs.render")
+    with torch.no_grad():
+        device = model.device
+        _dev = _renderer._dev
+        if cam_type != "PanopticSports":
+            raster_settings = GaussianRasterizationSettings(
+                image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
+                tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5), bg=bg_color,
+                scale_modifier=scaling_modifier, viewmatrix=_dev(viewpoint_camera.world_view_transform, device),
+                projmatrix=_dev(viewpoint_camera.full_proj_transform, device), sh_degree=model.active_sh_degree,
+                campos=_dev(viewpoint_camera.camera_center, device), prefiltered=False, debug=pipe.debug)
+            frame_time = float(viewpoint_camera.time)
+        else:
+            raster_settings = viewpoint_camera["camera"]
+            frame_time = float(viewpoint_camera["time"])
+        st, _ = model.state_at(frame_time, interp)
+        shs, colors = st.shs, None
+        if override_color is not None:
+            shs, colors = None, override_color.detach()
+            if model.perm is not None:
+                colors, = _deformation.permute_rows(model.perm, [colors.float()])
+        image, radii, depth, rstate = _rasterizer.rasterize_forward(raster_settings, st.xyz, shs, colors, st.opacity, st.scales, st.rotations,
+                                                                    None, expect_backward=False)
+        vis = rstate.visibility
+        if model.perm is not None:
+            radii, = _deformation.permute_rows(model.perm, [radii], scatter=True)
+            vis = radii > 0
+        out = {"render": image, "viewspace_points": None, "visibility_filter": vis, "radii": radii, "depth": depth}
+        if rgb8 is not None:
+            out["rgb8"] = to_rgb8(image, rgb8)
+        return out
+
+
 class Baked:
     """The deformed, activated state of a model at `times`, resident on the device: positions [N,3], scales [N,3] (exp applied), rotations
     [N,4] (unit quaternions), opacity [N,1] (sigmoid applied), SH [N,16,3] -- what the no-grad branch of render() hands to the rasterizer.
@@ -177,38 +219,7 @@ class Baked:
         included), the same result dict -- "viewspace_points" is None (nothing here takes a gradient), "radii" / "visibility_filter" are in
         the model's row order.  interp: what a time between two baked timestamps gets ("linear" | "nearest").  rgb8 = "trunc" | "round" adds
         "rgb8", the uint8 [H,W,3] image of to_rgb8.  The pipe's python SH / covariance paths are not available from a baked state."""
-        if pipe.compute_cov3D_python or pipe.convert_SHs_python:
-            raise NotImplementedError("Baked.render: pipe.compute_cov3D_python / pipe.convert_SHs_python need the live model; use fdgs.render")
-        with torch.no_grad():
-            device = self.device
-            _dev = _renderer._dev
-            if cam_type != "PanopticSports":
-                raster_settings = GaussianRasterizationSettings(
-                    image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
-                    tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5), bg=bg_color,
-                    scale_modifier=scaling_modifier, viewmatrix=_dev(viewpoint_camera.world_view_transform, device),
-                    projmatrix=_dev(viewpoint_camera.full_proj_transform, device), sh_degree=self.active_sh_degree,
-                    campos=_dev(viewpoint_camera.camera_center, device), prefiltered=False, debug=pipe.debug)
-                frame_time = float(viewpoint_camera.time)
-            else:
-                raster_settings = viewpoint_camera["camera"]
-                frame_time = float(viewpoint_camera["time"])
-            st, _ = self.state_at(frame_time, interp)
-            shs, colors = st.shs, None
-            if override_color is not None:
-                shs, colors = None, override_color.detach()
-                if self.perm is not None:
-                    colors, = _deformation.permute_rows(self.perm, [colors.float()])
-            image, radii, depth, rstate = _rasterizer.rasterize_forward(raster_settings, st.xyz, shs, colors, st.opacity, st.scales, st.rotations,
-                                                                        None, expect_backward=False)
-            vis = rstate.visibility
-            if self.perm is not None:
-                radii, = _deformation.permute_rows(self.perm, [radii], scatter=True)
-                vis = radii > 0
-            out = {"render": image, "viewspace_points": None, "visibility_filter": vis, "radii": radii, "depth": depth}
-            if rgb8 is not None:
-                out["rgb8"] = to_rgb8(image, rgb8)
-            return out
+        return _render_state(self, "Baked.render", viewpoint_camera, pipe, bg_color, scaling_modifier, override_color, cam_type, interp, rgb8)
 
 
 def bake(pc, times, max_bytes=None):
@@ -252,6 +263,207 @@ def bake(pc, times, max_bytes=None):
                     slots[h][k].copy_(o)
         frames = [BakedFrame([slots[h][k] for h in range(len(FIELDS))]) for k in range(T)]
     return Baked(ts, frames, head_on, perm, storage, pc.active_sh_degree)
+
+
+# ---- sparse bake: ONE full state, and per timestamp only the rows that move --------------------------------------------------------------
+
+def _checked_tol(tol):
+    try:
+        vals = tuple(float(v) for v in tol)
+    except TypeError:
+        vals = (float(tol),) * len(FIELDS)
+    if len(vals) != len(FIELDS):
+        raise ValueError("tol: one float, or one per field in the order of FIELDS (positions, scales, rotations, opacity, SH)")
+    if any(math.isnan(v) for v in vals):
+        raise ValueError("tol: NaN is not a tolerance")
+    return vals
+
+
+def sparse_bake_bytes(N, D, T, head_on):
+    """Bytes `bake_sparse` stores for N Gaussians of which D are dynamic, at T timestamps: one full state (all five fields, one padded slot
+    each), per timestamp one padded [D, width] slot of every field whose head is on, and the int32 row list."""
+    if N < 0 or T < 1 or not 0 <= D <= N or len(head_on) != len(FIELDS):
+        raise ValueError("sparse_bake_bytes: N >= 0, 0 <= D <= N, T >= 1 and one flag per field")
+    full = sum(_slot_floats(N, w) for w in FIELD_WIDTH)
+    per_time = sum(_slot_floats(D, w) for w, on in zip(FIELD_WIDTH, head_on) if on)
+    return 4 * (full + T * per_time + _slot_floats(D, 1))
+
+
+def _state_arrays(arrays, mask):
+    s = _lib.StateArrays()
+    for h, name in enumerate(FIELDS):
+        if mask >> h & 1:
+            setattr(s, name, arrays[h].data_ptr())
+    return s
+
+
+def _deformer(pc, net, head_on):
+    """(perm, forward): forward(t) is the five arrays of `bake`'s deformation forward at time t -- the same cfg, the same implicit Hilbert
+    permutation of the inputs, activate=True.  Call under torch.no_grad()."""
+    dn = net.deformation_net
+    planes, mlp = _deformation._collect(net)
+    cfg = dict(C=dn.grid.grid_config[0]["output_coordinate_dim"], L=len(dn.grid.grids), W=dn.W, head_on=head_on, activate=True,
+               save=False, grad=False, ordered=_deformation.spatial_order_hint(pc._xyz))
+    perm = _renderer._implicit_perm(pc, cfg, dn)
+    ins = [t.detach() for t in (pc.get_xyz, pc._scaling, pc._rotation, pc._opacity, pc._features_dc, pc._features_rest)]
+    if perm is not None:
+        cfg["ordered"] = True
+        ins = _deformation.permute_rows(perm, ins)
+
+    def forward(t):
+        st = _deformation.forward_impl(cfg, t, *ins, None, dn.grid.aabb, (*planes, *mlp), False)
+        return (st.o_xyz, st.o_sc, st.o_rot, st.o_op, st.o_sh)
+    return perm, forward
+
+
+def _extent_pass(forward, ts, head_on, N, device):
+    """(state at ts[0], extent [N,5] in the stored row order): one forward per timestamp, one fdgs_state_extent launch for each but the
+    first.  Two states are alive at a time."""
+    ref = forward(ts[0])
+    ext = torch.zeros(N, len(FIELDS), dtype=torch.float32, device=device)
+    mask = sum(1 << h for h, on in enumerate(head_on) if on)
+    for t in ts[1:]:
+        cur = forward(t)
+        _lib.check(_lib.lib().fdgs_state_extent(_lib.stream_ptr(), N, mask, _state_arrays(ref, mask), _state_arrays(cur, mask), _lib.ptr(ext)))
+    return ref, ext
+
+
+def _checked_model(pc, who):
+    net = pc._deformation
+    if not isinstance(net, _deformation.deform_network):
+        raise TypeError(f"{who}: pc._deformation must be this package's deform_network")
+    return net, _deformation._head_on(net.deformation_net.args), int(pc._xyz.shape[0])
+
+
+def motion_extent(pc, times):
+    """How far every Gaussian's baked state gets from its state at times[0] -> float32 [N,5] on the model's device, rows in the MODEL's
+    order: column h is the maximum, over the timestamps and the components of field h (the order of FIELDS), of |state_k - state_0| taken
+    as one float32 subtraction (fdgs_state_extent); 0 where head h is off; +inf where a difference is a NaN.  What `bake_sparse` compares
+    with `tol`: a quantile of a column is the tolerance that keeps that share of the rows static.  One deformation forward per timestamp,
+    exactly `bake`'s; two states of scratch, whatever len(times)."""
+    ts = _checked_times(times)
+    net, head_on, N = _checked_model(pc, "motion_extent")
+    with torch.no_grad():
+        perm, forward = _deformer(pc, net, head_on)
+        _, ext = _extent_pass(forward, ts, head_on, N, pc._xyz.device)
+        if perm is not None:
+            ext, = _deformation.permute_rows(perm, [ext], scatter=True)
+    return ext
+
+
+class SparseBaked:
+    """A baked sequence that keeps ONE full working state and, per timestamp, only the DYNAMIC rows: row n is dynamic iff for some head h
+    that is on motion_extent[n, h] > tol[h].  Stored bytes and the per-frame state update scale with D, the number of dynamic rows.
+
+    What a frame holds (`state_at`, `render`), against the dense `Baked` of the same model and times:
+      1. a dynamic row: at a baked timestamp the bits of the dense frame, at a time in between the bits `Baked.blend` gives that row;
+      2. a static row: the bits of the dense frame at times[0], at every time.  At every baked timestamp each of its components is
+         therefore within tol[h] of the dense frame (the difference taken as one float32 subtraction); between timestamps the linear fields
+         stay within that band up to rounding; the renormalised quaternion blend has no such bound, but a row whose rotation leaves the
+         band is dynamic anyway;
+      3. tol < 0: D == N and every frame, baked or blended, is bit for bit Baked.render's (image, depth, radii, visibility);
+      4. tol = inf: D == 0 and every frame is the frame at times[0], without a launch.
+
+    A SNAPSHOT like `Baked`.  `times`, `head_on`, `N`, `D`, `rows` (int32 [D], ascending, in the stored row order), `dynamic` (bool [N], the
+    model's row order), `perm` (the implicit Hilbert permutation the rows are stored in, or None), `tol` (5-tuple), `nbytes`
+    (== sparse_bake_bytes(N, D, len(times), head_on)), `active_sh_degree`, `launches` (fdgs_state_scatter launches so far), `device`."""
+
+    def __init__(self, times, head_on, perm, tol, working, arrays, compact_storage, compact, rows, dynamic, active_sh_degree):
+        self.times, self.head_on, self.perm, self.tol = tuple(times), tuple(head_on), perm, tuple(tol)
+        self._working, self._compact_storage, self._compact = working, compact_storage, compact
+        self.rows, self.dynamic = rows, dynamic
+        self.active_sh_degree = active_sh_degree
+        self.N, self.D = int(arrays[0].shape[0]), int(rows.shape[0])
+        self.nbytes = 4 * (working.numel() + compact_storage.numel())
+        self.launches = 0
+        self._mask = sum(1 << h for h, on in enumerate(self.head_on) if on)
+        self._frame = BakedFrame(arrays)
+        self._shown = (0, 0, 0.0)               # the (i, j, w) the dynamic rows of the working state hold
+
+    @property
+    def device(self):
+        return self._working.device
+
+    def state_at(self, t, interp="linear"):
+        """(BakedFrame over the working state, (i, j, w)) for frame time t.  ONE fdgs_state_scatter launch (a copy of compact[i] at a baked
+        timestamp or with interp="nearest", else the blend of compact[i] and compact[j] fused into it) when (i, j, w) is not what the
+        working state holds; none when it is, when D == 0 or when no head is on.  The frame is overwritten by the next call."""
+        if interp not in ("linear", "nearest"):
+            raise ValueError(f"interp: 'linear' or 'nearest', not {interp!r}")
+        key = _locate(self.times, t, interp)
+        if self.D and self._mask and key != self._shown:
+            i, j, w = key
+            blend = i != j
+            a, b = _state_arrays(self._compact[i], self._mask), _state_arrays(self._compact[j], self._mask)
+            _lib.check(_lib.lib().fdgs_state_scatter(_lib.stream_ptr(), self.D, _lib.ptr(self.rows), self.N, self._mask, a, b if blend else None,
+                                                     float(w) if blend else 0.0, _state_arrays(self._frame.arrays(), self._mask)))
+            self.launches += 1
+            self._shown = key
+        return self._frame, key
+
+    def render(self, viewpoint_camera, pipe, bg_color, scaling_modifier=1.0, override_color=None, cam_type=None, interp="linear", rgb8=None):
+        """The contract of `Baked.render`, on the state `state_at` gives."""
+        return _render_state(self, "SparseBaked.render", viewpoint_camera, pipe, bg_color, scaling_modifier, override_color, cam_type, interp,
+                             rgb8)
+
+
+def bake_sparse(pc, times, tol, max_bytes=None):
+    """`bake` for a sequence in which much of the set hardly moves -> SparseBaked (its guarantees are listed there).
+
+    tol: a float, or five in the order of FIELDS; absolute (world units for positions and scales, quaternion components, opacity, SH
+    coefficients).  A negative value makes every row dynamic, math.inf keeps that field from deciding, NaN raises ValueError.
+    Two passes over the timestamps, 2 * len(times) deformation forwards, so that the dense T x N storage never exists: the first puts the
+    state at times[0] into the full working state and accumulates the extents (fdgs_state_extent), after which the list of dynamic rows is
+    read back (the one synchronisation); the second deforms every timestamp again -- the forward is deterministic -- and keeps the dynamic
+    rows (fdgs_state_gather).  Raises MemoryError, before allocating, when `max_bytes` is given and the full state alone exceeds it, and
+    again when the full state and the compact rows do."""
+    ts = _checked_times(times)
+    tol = _checked_tol(tol)
+    net, head_on, N = _checked_model(pc, "bake_sparse")
+    T = len(ts)
+    need = sparse_bake_bytes(N, 0, T, head_on)
+    if max_bytes is not None and need > max_bytes:
+        raise MemoryError(f"bake_sparse: the full state of {N} Gaussians needs {need} bytes, max_bytes = {max_bytes}")
+    device = pc._xyz.device
+    on = [h for h in range(len(FIELDS)) if head_on[h]]
+    mask = sum(1 << h for h in on)
+    with torch.no_grad():
+        perm, forward = _deformer(pc, net, head_on)
+        working = torch.empty(need // 4, dtype=torch.float32, device=device)
+        arrays, off = [], 0
+        for w, shp in zip(FIELD_WIDTH, FIELD_SHAPE):
+            arrays.append(working[off:off + N * w].view(N, *shp))
+            off += _slot_floats(N, w)
+        first, ext = _extent_pass(forward, ts, head_on, N, device)
+        for dst, src in zip(arrays, first):
+            dst.copy_(src)
+        del first
+        dyn = torch.zeros(N, dtype=torch.bool, device=device)
+        for h in on:
+            dyn |= ext[:, h] > tol[h]
+        del ext
+        found = torch.nonzero(dyn).reshape(-1).to(torch.int32)          # ascending; the one read-back
+        D = int(found.shape[0])
+        need = sparse_bake_bytes(N, D, T, head_on)
+        if max_bytes is not None and need > max_bytes:
+            raise MemoryError(f"bake_sparse: {D} dynamic rows of {N} at {T} timestamps need {need} bytes, max_bytes = {max_bytes}")
+        storage = torch.empty(need // 4 - working.numel(), dtype=torch.float32, device=device)
+        compact, off = [[None] * len(FIELDS) for _ in range(T)], 0
+        for h in on:
+            stride = _slot_floats(D, FIELD_WIDTH[h])
+            for k in range(T):
+                compact[k][h] = storage[off + k * stride:off + k * stride + D * FIELD_WIDTH[h]].view(D, *FIELD_SHAPE[h])
+            off += stride * T
+        rows = storage[off:off + D].view(torch.int32)
+        rows.copy_(found)
+        if D and mask:
+            for k, t in enumerate(ts):
+                cur = forward(t)
+                _lib.check(_lib.lib().fdgs_state_gather(_lib.stream_ptr(), D, _lib.ptr(rows), N, mask, _state_arrays(cur, mask),
+                                                        _state_arrays(compact[k], mask)))
+        if perm is not None:
+            dyn = _deformation.permute_rows(perm, [dyn.to(torch.int32)], scatter=True)[0] != 0
+    return SparseBaked(ts, head_on, perm, tol, working, arrays, storage, compact, rows, dyn, pc.active_sh_degree)
 
 
 def pack_ply_rows(xyz, scales, rotations, opacity, shs):

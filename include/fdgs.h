@@ -559,6 +559,44 @@ int fdgs_state_place(void* stream, const fdgs_placement* p, int N, unsigned fiel
 int fdgs_state_place_host(const fdgs_placement* p, int N, unsigned field_mask, const fdgs_state_arrays* a,
                           const fdgs_state_arrays* b, float w, const fdgs_state_arrays* out);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Sparse baked playback (additions to ABI 6; no existing signature changed): a baked sequence that keeps ONE full state and, per
+ * timestamp, only the rows that move (csrc/playback.hip, fdgs.playback.bake_sparse).  Three operations over fdgs_state_arrays with the
+ * field-mask convention of fdgs_state_place: bit h of field_mask selects field h (positions, scales, rotations, opacity, SH); a field
+ * that is not selected is neither read nor written and its pointers may be NULL.  The arithmetic is host/device functions of
+ * csrc/playback_ops.h compiled without contraction: every *_host twin returns, over host arrays, bit for bit what the device writes.
+ *
+ *   rows        a device int32[D], STRICTLY ASCENDING, every entry in [0, N)
+ *   a, b, compact   arrays of D rows ([D, width]);   full, out, ref, cur   arrays of N rows ([N, width])
+ *   alignment   rotations and SH 16-byte aligned on both sides (a lane moves 16 bytes), positions, scales and opacity 4-byte aligned;
+ *               the *_host twins take host pointers of any alignment
+ *   out overlaps neither a nor b
+ *
+ * D = 0, N = 0 or field_mask = 0 succeed without a launch; otherwise ONE launch on `stream`, nothing synchronises.  FDGS_E_INVALID with a
+ * message, before anything is launched or written: a NULL required pointer; D < 0, N < 0 or D > N; w outside [0, 1] or NaN;
+ * b == NULL with w != 0; a field_mask above 31; a misaligned rotation or SH pointer (device entry points).
+ * The device entry points cannot inspect `rows`: the kernels compare every row index, as an unsigned number, against N and SKIP a row
+ * that fails, so a bad list cannot store (or load) out of bounds -- what it does store is unspecified.  The *_host twins validate the
+ * list (range, strictly ascending) and return FDGS_E_INVALID without writing anything. */
+/* extent[n][h] (float32 [N,5], caller zero-fills before the first call) = running maximum, over calls and over the components c of
+ * field h in ascending order, of |cur_h[n][c] - ref_h[n][c]|:   d = cur - ref;  m = fabsf(d);  m != m ? e = +inf : (m > e ? e = m : e)
+ * (a NaN difference -- a NaN component, inf - inf -- makes the extent +inf).  Columns of unselected fields are left untouched.
+ * One launch. */
+int fdgs_state_extent(void* stream, int N, unsigned field_mask, const fdgs_state_arrays* ref, const fdgs_state_arrays* cur, float* extent);
+int fdgs_state_extent_host(int N, unsigned field_mask, const fdgs_state_arrays* ref, const fdgs_state_arrays* cur, float* extent);
+/* compact_h[r] = full_h[rows[r]], r = 0 .. D-1: bit copies.  One launch. */
+int fdgs_state_gather(void* stream, int D, const int32_t* rows, int N, unsigned field_mask, const fdgs_state_arrays* full,
+                      const fdgs_state_arrays* compact);
+int fdgs_state_gather_host(int D, const int32_t* rows, int N, unsigned field_mask, const fdgs_state_arrays* full,
+                           const fdgs_state_arrays* compact);
+/* out_h[rows[r]] = a_h[r] (b == NULL, w must be 0: bit copies) or the blend of a_h[r] and b_h[r] at weight w in [0, 1], by blend_lerp /
+ * blend_quat of playback_ops.h, i.e. exactly what fdgs_state_blend writes for those two rows.  Rows of `out` that are not listed are
+ * not touched.  One launch. */
+int fdgs_state_scatter(void* stream, int D, const int32_t* rows, int N, unsigned field_mask, const fdgs_state_arrays* a,
+                       const fdgs_state_arrays* b, float w, const fdgs_state_arrays* out);
+int fdgs_state_scatter_host(int D, const int32_t* rows, int N, unsigned field_mask, const fdgs_state_arrays* a,
+                            const fdgs_state_arrays* b, float w, const fdgs_state_arrays* out);
+
 #ifdef __cplusplus
 }
 #endif
