@@ -22,11 +22,9 @@ import torch
 
 from . import _lib
 from . import deformation as _deformation
-from . import rasterizer as _rasterizer
-from . import renderer as _renderer
 from . import sh as _sh
-from .playback import FIELD_SHAPE, FIELD_WIDTH, FIELDS, BakedFrame, SparseBaked, _locate, _slot_floats, to_rgb8
-from .rasterizer import GaussianRasterizationSettings
+from .playback import (BakedFrame, SparseBaked, _carve, _checked_interp, _field_mask, _field_slots, _locate, _perm_maps, _render_state,
+                       _state_arrays)
 
 WRAPS = ("clamp", "loop", "pingpong")
 _SH_ZERO = 1e-13        # entries of a band matrix below this are structural zeros of the rotation (the solve leaves ~1e-16 there)
@@ -183,8 +181,7 @@ def compose_bytes(Ns):
     Ns = [int(n) for n in Ns]
     if not Ns or any(n < 0 for n in Ns):
         raise ValueError("compose_bytes: at least one model, N >= 0")
-    total = sum(Ns)
-    return 4 * sum(_slot_floats(total, w) for w in FIELD_WIDTH)
+    return 4 * _carve(_field_slots(sum(Ns)))[0]
 
 
 class Composite:
@@ -213,6 +210,9 @@ class Composite:
         self._structs = [p.struct(m.active_sh_degree) for p, m in zip(self.placements, self.models)]
         self._shown = [None] * len(self.models)          # per model: the (i, j, w) its time-dependent rows hold
         self._frame = BakedFrame(arrays)
+        self._masks = [_field_mask(m.head_on) for m in self.models]         # per model: its time-dependent fields
+        self._maps = self._row_maps()
+        self._targets = {}          # (m, mask) -> the fdgs_state_arrays of model m's rows: they never change, filled on first use
 
     @property
     def device(self):
@@ -222,13 +222,10 @@ class Composite:
         model = self.models[m]
         if mask == 0 or model.N == 0:
             return
-        a, b, out = _lib.StateArrays(), _lib.StateArrays(), _lib.StateArrays()
-        fa, fb = model.frames[i], model.frames[j]
-        for h, name in enumerate(FIELDS):
-            if mask >> h & 1:
-                setattr(a, name, getattr(fa, name).data_ptr())
-                setattr(b, name, getattr(fb, name).data_ptr())
-                setattr(out, name, self._arrays[h].data_ptr() + 4 * self.offsets[m] * FIELD_WIDTH[h])
+        a, b = _state_arrays(model.frames[i].arrays(), mask), _state_arrays(model.frames[j].arrays(), mask)
+        out = self._targets.get((m, mask))
+        if out is None:
+            out = self._targets[m, mask] = _state_arrays(self._arrays, mask, self.offsets[m])
         blend = i != j
         _lib.check(_lib.lib().fdgs_state_place(_lib.stream_ptr(), self._structs[m], model.N, mask, a, b if blend else None,
                                                float(w) if blend else 0.0, out))
@@ -238,10 +235,8 @@ class Composite:
         """The composite state at frame time t as a BakedFrame over this object's arrays (overwritten by the next call): per model, ONE
         fdgs_state_place launch for its time-dependent fields, straight from the two baked frames that bracket map_time(times, t,
         placement) with the blend fused -- or no launch when that model's (i, j, w) is what its rows already hold."""
-        if interp not in ("linear", "nearest"):
-            raise ValueError(f"interp: 'linear' or 'nearest', not {interp!r}")
-        for m, (model, pl) in enumerate(zip(self.models, self.placements)):
-            mask = sum(1 << h for h, on in enumerate(model.head_on) if on)
+        _checked_interp(interp)
+        for m, (model, pl, mask) in enumerate(zip(self.models, self.placements, self._masks)):
             if mask == 0:
                 continue
             key = _locate(model.times, map_time(model.times, t, pl), interp)
@@ -254,41 +249,18 @@ class Composite:
         """The contract of `Baked.render` for the whole scene: the same raster settings (the PanopticSports dict camera included), the same
         result dict.  "radii" / "visibility_filter" have sum(N) entries, model m's at `slices[m]` in that model's own row order (segments
         of models stored through a permutation are scattered back); `override_color` is [sum(N), 3] in the same order."""
-        if pipe.compute_cov3D_python or pipe.convert_SHs_python:
-            raise NotImplementedError("Composite.render: pipe.compute_cov3D_python / pipe.convert_SHs_python need the live model; use fdgs.render")
-        with torch.no_grad():
-            device = self.device
-            _dev = _renderer._dev
-            if cam_type != "PanopticSports":
-                raster_settings = GaussianRasterizationSettings(
-                    image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
-                    tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5), bg=bg_color,
-                    scale_modifier=scaling_modifier, viewmatrix=_dev(viewpoint_camera.world_view_transform, device),
-                    projmatrix=_dev(viewpoint_camera.full_proj_transform, device), sh_degree=self.active_sh_degree,
-                    campos=_dev(viewpoint_camera.camera_center, device), prefiltered=False, debug=pipe.debug)
-                frame_time = float(viewpoint_camera.time)
-            else:
-                raster_settings = viewpoint_camera["camera"]
-                frame_time = float(viewpoint_camera["time"])
-            st = self.state_at(frame_time, interp)
-            permuted = any(m.perm is not None for m in self.models)
-            shs, colors = st.shs, None
-            if override_color is not None:
-                shs, colors = None, override_color.detach().float()
-                if permuted:
-                    colors = torch.cat([c if m.perm is None else _deformation.permute_rows(m.perm, [c.contiguous()])[0]
-                                        for m, c in ((m, colors[sl]) for m, sl in zip(self.models, self.slices))])
-            image, radii, depth, rstate = _rasterizer.rasterize_forward(raster_settings, st.xyz, shs, colors, st.opacity, st.scales, st.rotations,
-                                                                        None, expect_backward=False)
-            vis = rstate.visibility
-            if permuted:
-                radii = torch.cat([r if m.perm is None else _deformation.permute_rows(m.perm, [r.contiguous()], scatter=True)[0]
-                                   for m, r in ((m, radii[sl]) for m, sl in zip(self.models, self.slices))])
-                vis = radii > 0
-            out = {"render": image, "viewspace_points": None, "visibility_filter": vis, "radii": radii, "depth": depth}
-            if rgb8 is not None:
-                out["rgb8"] = to_rgb8(image, rgb8)
-            return out
+        return _render_state("Composite.render", lambda t: self.state_at(t, interp), self.active_sh_degree, self.device, *self._maps,
+                             viewpoint_camera, pipe, bg_color, scaling_modifier, override_color, cam_type, rgb8)
+
+    def _row_maps(self):
+        """playback._perm_maps for the whole scene: model m's rows, `slices[m]`, go through model m's own permutation."""
+        if all(m.perm is None for m in self.models):
+            return None, None
+        maps = [_perm_maps(m.perm) for m in self.models]
+
+        def through(k):
+            return lambda t: torch.cat([t[sl] if mp[k] is None else mp[k](t[sl]) for mp, sl in zip(maps, self.slices)])
+        return through(0), through(1)
 
 
 def compose(models, placements=None, max_bytes=None):
@@ -321,11 +293,8 @@ def compose(models, placements=None, max_bytes=None):
     total = sum(m.N for m in models)
     with torch.no_grad():
         storage = torch.empty(need // 4, dtype=torch.float32, device=device)
-        arrays, off = [], 0
-        for w, shp in zip(FIELD_WIDTH, FIELD_SHAPE):
-            arrays.append(storage[off:off + total * w].view(total, *shp))
-            off += _slot_floats(total, w)
+        arrays = [v[0] for v in _carve(_field_slots(total), storage)[1]]
         scene = Composite(models, placements, storage, arrays)
         for m, model in enumerate(models):
-            scene._place(m, sum(1 << h for h, on in enumerate(model.head_on) if not on), 0, 0, 0.0)
+            scene._place(m, _field_mask([not on for on in model.head_on]), 0, 0, 0.0)
     return scene

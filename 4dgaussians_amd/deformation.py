@@ -199,6 +199,18 @@ def _collect(net):
     return planes, mlp
 
 
+def _forward_cfg(dn, xyz, activate, ordered=None):
+    """The `cfg` of one deformation forward through `dn` (net.deformation_net of a deform_network), built HERE for deform(), render(),
+    render_views() and the baked playback alike: a baked frame is render()'s no-grad frame bit for bit only while they agree on it.
+    Grad mode is read at call time: inside autograd.Function.forward it is always off, and needs_input_grad stays True under
+    torch.no_grad() -- evaluation frames (render.py, training_report) must not allocate ~3.2 KB per Gaussian of saved activations nor
+    take the slower saving forward.  `ordered`: see deform()."""
+    grid, grad = dn.grid, torch.is_grad_enabled()
+    return dict(C=grid.grid_config[0]["output_coordinate_dim"], L=len(grid.grids), W=dn.W, head_on=_head_on(dn.args),
+                activate=bool(activate), save=bool(SAVE_ACTIVATIONS and grad), grad=grad,
+                ordered=spatial_order_hint(xyz) if ordered is None else bool(ordered))
+
+
 def deform(net, xyz, scales, rotations, opacity, shs=None, shs_dc=None, shs_rest=None, time=None, activate=False, ordered=None):
     """Runs the fused deformation.  Either `shs` ([N,16,3]) or the pair (shs_dc [N,1,3], shs_rest [N,15,3]) is given
     (the pair skips the torch.cat of GaussianModel.get_features, scene/gaussian_model.py:121-124).  `time` is a python
@@ -208,13 +220,7 @@ def deform(net, xyz, scales, rotations, opacity, shs=None, shs_dc=None, shs_rest
     once per position tensor, see spatial_order_hint) -- selects the plane-gradient kernel, never the result."""
     planes, mlp = _collect(net)
     dn = net.deformation_net
-    cfg = dict(C=dn.grid.grid_config[0]["output_coordinate_dim"], L=len(dn.grid.grids), W=dn.W,
-               head_on=_head_on(dn.args), activate=bool(activate),
-               # grad mode is read HERE: inside autograd.Function.forward it is always off, and needs_input_grad stays True
-               # under torch.no_grad() -- evaluation frames (render.py, training_report) must not allocate ~3.2 KB per
-               # Gaussian of saved activations nor take the slower saving forward
-               save=bool(SAVE_ACTIVATIONS and torch.is_grad_enabled()),
-               ordered=spatial_order_hint(xyz) if ordered is None else bool(ordered))
+    cfg = _forward_cfg(dn, xyz, activate, ordered)
     if isinstance(time, torch.Tensor):
         t_tensor, t_scalar = time, 0.0
     else:

@@ -34,7 +34,6 @@ from . import deformation as _deformation
 from . import io as _io
 from . import rasterizer as _rasterizer
 from . import renderer as _renderer
-from .rasterizer import GaussianRasterizationSettings
 
 FIELDS = ("xyz", "scales", "rotations", "opacity", "shs")          # in the order of deformation.HEAD_NAMES: head h moves field h
 FIELD_WIDTH = _deformation.HEAD_K                                   # floats per Gaussian: 3, 3, 4, 1, 48
@@ -44,8 +43,28 @@ FIELD_SHAPE = ((3,), (3,), (4,), (1,), (16, 3))
 SLOT_ALIGN_FLOATS = 64
 
 
-def _slot_floats(N, width):
-    return (N * width + SLOT_ALIGN_FLOATS - 1) // SLOT_ALIGN_FLOATS * SLOT_ALIGN_FLOATS
+def _carve(slots, buf=None):
+    """THE slot layout: `slots`, a sequence of (rows, row shape, copies), laid out back to back in a flat float32 buffer, every array
+    starting on a multiple of SLOT_ALIGN_FLOATS -> (floats needed, per slot the list of its `copies` [rows, *shape] views of `buf`).
+    Without a buffer it only counts, which is how the *_bytes functions and the allocations agree."""
+    off, views = 0, []
+    for rows, shape, copies in slots:
+        n = rows * math.prod(shape)
+        stride = (n + SLOT_ALIGN_FLOATS - 1) // SLOT_ALIGN_FLOATS * SLOT_ALIGN_FLOATS
+        if buf is not None:
+            views.append([buf[off + k * stride:off + k * stride + n].view(rows, *shape) for k in range(copies)])
+        off += stride * copies
+    return off, views
+
+
+def _field_slots(N, copies=(1,) * len(FIELDS)):
+    """One slot per field of FIELDS for _carve: [N, *FIELD_SHAPE[h]], copies[h] times (0: no floats, an empty list of views)."""
+    return [(N, shape, c) for shape, c in zip(FIELD_SHAPE, copies)]
+
+
+def _field_mask(head_on):
+    """Bit h set for every field whose head is on: the `mask` of the fdgs_state_* calls."""
+    return sum(1 << h for h, on in enumerate(head_on) if on)
 
 
 def bake_bytes(N, T, head_on):
@@ -53,7 +72,7 @@ def bake_bytes(N, T, head_on):
     rotations, opacity, SH) takes one padded slot per timestamp, a field whose head is off one slot in all."""
     if N < 0 or T < 1 or len(head_on) != len(FIELDS):
         raise ValueError("bake_bytes: N >= 0, T >= 1 and one flag per field")
-    return 4 * sum(_slot_floats(N, w) * (T if on else 1) for w, on in zip(FIELD_WIDTH, head_on))
+    return 4 * _carve(_field_slots(N, [T if on else 1 for on in head_on]))[0]
 
 
 def _checked_times(times):
@@ -63,6 +82,12 @@ def _checked_times(times):
     if any(math.isnan(t) or math.isinf(t) for t in ts) or any(b <= a for a, b in zip(ts, ts[1:])):
         raise ValueError("times: a strictly increasing sequence of finite floats")
     return ts
+
+
+def _checked_interp(interp):
+    if interp not in ("linear", "nearest"):
+        raise ValueError(f"interp: 'linear' or 'nearest', not {interp!r}")
+    return interp
 
 
 def _locate(ts, t, interp):
@@ -81,9 +106,7 @@ def locate(times, t, interp="linear"):
     """Where frame time `t` falls in the strictly increasing `times` (pure Python, float64): (i, j, w) such that the state at t is
     state_i + w * (state_j - state_i).  t is clamped to [times[0], times[-1]]; t == times[i] gives (i, i, 0.0); interp="linear" gives the
     bracketing pair and w = (t - t_i) / (t_j - t_i); interp="nearest" gives (k, k, 0.0) for the nearer timestamp, the lower one on a tie."""
-    if interp not in ("linear", "nearest"):
-        raise ValueError(f"interp: 'linear' or 'nearest', not {interp!r}")
-    return _locate(_checked_times(times), t, interp)
+    return _locate(_checked_times(times), t, _checked_interp(interp))
 
 
 def to_rgb8(image, mode="trunc"):
@@ -113,39 +136,36 @@ class BakedFrame:
             setattr(self, name, a)
 
     def arrays(self):
-        return tuple(getattr(self, name) for name in FIELDS)
+        return (self.xyz, self.scales, self.rotations, self.opacity, self.shs)
 
 
-def _render_state(model, who, viewpoint_camera, pipe, bg_color, scaling_modifier, override_color, cam_type, interp, rgb8):
-    """The body of Baked.render and SparseBaked.render: the rasterizer on `model.state_at(frame time, interp)`.  `model` has `device`,
-    `perm`, `active_sh_degree` and `state_at`."""
+def _perm_maps(perm):
+    """The two row maps of _render_state for rows stored through `perm`: (model order -> stored order, stored order -> model order)."""
+    if perm is None:
+        return None, None
+    return (lambda t: _deformation.permute_rows(perm, [t])[0]), (lambda t: _deformation.permute_rows(perm, [t], scatter=True)[0])
+
+
+def _render_state(who, frame_at, sh_degree, device, to_stored, to_model, viewpoint_camera, pipe, bg_color, scaling_modifier, override_color,
+                  cam_type, rgb8):
+    """The body of Baked.render, SparseBaked.render and Composite.render: the rasterizer on the BakedFrame `frame_at(frame time)`.
+    `to_stored` / `to_model` (None: the rows are stored in the model's order) take `override_color` to the stored row order and bring
+    `radii` back."""
     if pipe.compute_cov3D_python or pipe.convert_SHs_python:
         raise NotImplementedError(f"{who}: pipe.compute_cov3D_python / pipe.convert_SHs_python need the live model; use fdgs.render")
     with torch.no_grad():
-        device = model.device
-        _dev = _renderer._dev
-        if cam_type != "PanopticSports":
-            raster_settings = GaussianRasterizationSettings(
-                image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
-                tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5), bg=bg_color,
-                scale_modifier=scaling_modifier, viewmatrix=_dev(viewpoint_camera.world_view_transform, device),
-                projmatrix=_dev(viewpoint_camera.full_proj_transform, device), sh_degree=model.active_sh_degree,
-                campos=_dev(viewpoint_camera.camera_center, device), prefiltered=False, debug=pipe.debug)
-            frame_time = float(viewpoint_camera.time)
-        else:
-            raster_settings = viewpoint_camera["camera"]
-            frame_time = float(viewpoint_camera["time"])
-        st, _ = model.state_at(frame_time, interp)
+        raster_settings, frame_time = _renderer._frame_settings(viewpoint_camera, cam_type, bg_color, scaling_modifier, sh_degree, device, pipe)
+        st = frame_at(frame_time)
         shs, colors = st.shs, None
         if override_color is not None:
-            shs, colors = None, override_color.detach()
-            if model.perm is not None:
-                colors, = _deformation.permute_rows(model.perm, [colors.float()])
+            shs, colors = None, override_color.detach().float()
+            if to_stored is not None:
+                colors = to_stored(colors)
         image, radii, depth, rstate = _rasterizer.rasterize_forward(raster_settings, st.xyz, shs, colors, st.opacity, st.scales, st.rotations,
                                                                     None, expect_backward=False)
         vis = rstate.visibility
-        if model.perm is not None:
-            radii, = _deformation.permute_rows(model.perm, [radii], scatter=True)
+        if to_model is not None:
+            radii = to_model(radii)
             vis = radii > 0
         out = {"render": image, "viewspace_points": None, "visibility_filter": vis, "radii": radii, "depth": depth}
         if rgb8 is not None:
@@ -170,7 +190,7 @@ class Baked:
         self.active_sh_degree = active_sh_degree
         self.N = int(frames[0].xyz.shape[0])
         self.nbytes = storage.numel() * storage.element_size()
-        self._scratch = None
+        self._scratch, self._maps = None, _perm_maps(perm)
 
     @property
     def device(self):
@@ -180,16 +200,10 @@ class Baked:
         """The state at weight `w` between frames i and j as a BakedFrame: ONE fdgs_state_blend launch into this object's scratch state
         (time-dependent fields only; the others are the stored arrays themselves).  The result is overwritten by the next blend."""
         if self._scratch is None:
-            dev = self.device
-            buf = torch.empty(sum(_slot_floats(self.N, wd) for wd, on in zip(FIELD_WIDTH, self.head_on) if on), dtype=torch.float32, device=dev)
-            arrays, off = [], 0
-            for wd, shp, on, static in zip(FIELD_WIDTH, FIELD_SHAPE, self.head_on, self.frames[0].arrays()):
-                if on:
-                    arrays.append(buf[off:off + self.N * wd].view(self.N, *shp))
-                    off += _slot_floats(self.N, wd)
-                else:
-                    arrays.append(static)
-            self._scratch = (buf, BakedFrame(arrays))
+            slots = _field_slots(self.N, [1 if on else 0 for on in self.head_on])
+            buf = torch.empty(_carve(slots)[0], dtype=torch.float32, device=self.device)
+            views = _carve(slots, buf)[1]
+            self._scratch = (buf, BakedFrame([v[0] if v else static for v, static in zip(views, self.frames[0].arrays())]))
         out = self._scratch[1]
         a, b = self.frames[i], self.frames[j]
         streams = (_lib.BlendStream * _lib.MAX_BLEND_STREAMS)()
@@ -206,9 +220,7 @@ class Baked:
 
     def state_at(self, t, interp="linear"):
         """(BakedFrame, (i, j, w)) for frame time t: a stored frame when t is a baked timestamp (or interp="nearest"), else the blend."""
-        if interp not in ("linear", "nearest"):
-            raise ValueError(f"interp: 'linear' or 'nearest', not {interp!r}")
-        i, j, w = _locate(self.times, t, interp)
+        i, j, w = _locate(self.times, t, _checked_interp(interp))
         if i == j or not any(self.head_on):
             return self.frames[i], (i, j, w)
         return self.blend(i, j, w), (i, j, w)
@@ -219,7 +231,8 @@ class Baked:
         included), the same result dict -- "viewspace_points" is None (nothing here takes a gradient), "radii" / "visibility_filter" are in
         the model's row order.  interp: what a time between two baked timestamps gets ("linear" | "nearest").  rgb8 = "trunc" | "round" adds
         "rgb8", the uint8 [H,W,3] image of to_rgb8.  The pipe's python SH / covariance paths are not available from a baked state."""
-        return _render_state(self, "Baked.render", viewpoint_camera, pipe, bg_color, scaling_modifier, override_color, cam_type, interp, rgb8)
+        return _render_state("Baked.render", lambda t: self.state_at(t, interp)[0], self.active_sh_degree, self.device, *self._maps,
+                             viewpoint_camera, pipe, bg_color, scaling_modifier, override_color, cam_type, rgb8)
 
 
 def bake(pc, times, max_bytes=None):
@@ -231,34 +244,18 @@ def bake(pc, times, max_bytes=None):
     first frame: they do not depend on the time).  Raises ValueError unless `times` is strictly increasing, MemoryError -- before anything
     is allocated -- when `max_bytes` is given and bake_bytes(...) exceeds it."""
     ts = _checked_times(times)
-    net = pc._deformation
-    if not isinstance(net, _deformation.deform_network):
-        raise TypeError("bake: pc._deformation must be this package's deform_network")
-    dn = net.deformation_net
-    head_on = _deformation._head_on(dn.args)
-    N, T = int(pc._xyz.shape[0]), len(ts)
+    head_on, N = _checked_model(pc, "bake")
+    T = len(ts)
     need = bake_bytes(N, T, head_on)
     if max_bytes is not None and need > max_bytes:
         raise MemoryError(f"bake: {T} timestamps of {N} Gaussians need {need} bytes, max_bytes = {max_bytes}")
     with torch.no_grad():
-        planes, mlp = _deformation._collect(net)
-        cfg = dict(C=dn.grid.grid_config[0]["output_coordinate_dim"], L=len(dn.grid.grids), W=dn.W, head_on=head_on, activate=True,
-                   save=False, grad=False, ordered=_deformation.spatial_order_hint(pc._xyz))
-        perm = _renderer._implicit_perm(pc, cfg, dn)
-        ins = [t.detach() for t in (pc.get_xyz, pc._scaling, pc._rotation, pc._opacity, pc._features_dc, pc._features_rest)]
-        if perm is not None:
-            cfg["ordered"] = True
-            ins = _deformation.permute_rows(perm, ins)
+        perm, forward = _deformer(pc)
         storage = torch.empty(need // 4, dtype=torch.float32, device=pc._xyz.device)
-        slots, off = [], 0          # per field: the [N, ...] view of every timestamp (one shared view when the head is off)
-        for w, shp, on in zip(FIELD_WIDTH, FIELD_SHAPE, head_on):
-            stride = _slot_floats(N, w)
-            views = [storage[off + k * stride:off + k * stride + N * w].view(N, *shp) for k in range(T if on else 1)]
-            slots.append(views if on else views * T)
-            off += stride * (T if on else 1)
+        # per field: the [N, ...] view of every timestamp (one shared view when the head is off)
+        slots = [v if on else v * T for v, on in zip(_carve(_field_slots(N, [T if on else 1 for on in head_on]), storage)[1], head_on)]
         for k, t in enumerate(ts):
-            st = _deformation.forward_impl(cfg, t, *ins, None, dn.grid.aabb, (*planes, *mlp), False)
-            for h, o in enumerate((st.o_xyz, st.o_sc, st.o_rot, st.o_op, st.o_sh)):
+            for h, o in enumerate(forward(t)):
                 if head_on[h] or k == 0:
                     slots[h][k].copy_(o)
         frames = [BakedFrame([slots[h][k] for h in range(len(FIELDS))]) for k in range(T)]
@@ -284,34 +281,31 @@ def sparse_bake_bytes(N, D, T, head_on):
     each), per timestamp one padded [D, width] slot of every field whose head is on, and the int32 row list."""
     if N < 0 or T < 1 or not 0 <= D <= N or len(head_on) != len(FIELDS):
         raise ValueError("sparse_bake_bytes: N >= 0, 0 <= D <= N, T >= 1 and one flag per field")
-    full = sum(_slot_floats(N, w) for w in FIELD_WIDTH)
-    per_time = sum(_slot_floats(D, w) for w, on in zip(FIELD_WIDTH, head_on) if on)
-    return 4 * (full + T * per_time + _slot_floats(D, 1))
+    return 4 * (_carve(_field_slots(N))[0] + _carve(_compact_slots(D, T, head_on))[0])
 
 
-def _state_arrays(arrays, mask):
+def _compact_slots(D, T, head_on):
+    """What bake_sparse keeps beside the full state: [D, ...] of every field whose head is on at every timestamp, then the D int32 rows."""
+    return _field_slots(D, [T if on else 0 for on in head_on]) + [(D, (), 1)]
+
+
+def _state_arrays(arrays, mask, row_offset=0):
+    """fdgs_state_arrays over the five `arrays` from row `row_offset` on: the pointers of the fields `mask` selects, NULL elsewhere."""
     s = _lib.StateArrays()
     for h, name in enumerate(FIELDS):
         if mask >> h & 1:
-            setattr(s, name, arrays[h].data_ptr())
+            p = arrays[h].data_ptr()
+            setattr(s, name, p + 4 * row_offset * FIELD_WIDTH[h] if row_offset else p)
     return s
 
 
-def _deformer(pc, net, head_on):
-    """(perm, forward): forward(t) is the five arrays of `bake`'s deformation forward at time t -- the same cfg, the same implicit Hilbert
-    permutation of the inputs, activate=True.  Call under torch.no_grad()."""
-    dn = net.deformation_net
-    planes, mlp = _deformation._collect(net)
-    cfg = dict(C=dn.grid.grid_config[0]["output_coordinate_dim"], L=len(dn.grid.grids), W=dn.W, head_on=head_on, activate=True,
-               save=False, grad=False, ordered=_deformation.spatial_order_hint(pc._xyz))
-    perm = _renderer._implicit_perm(pc, cfg, dn)
-    ins = [t.detach() for t in (pc.get_xyz, pc._scaling, pc._rotation, pc._opacity, pc._features_dc, pc._features_rest)]
-    if perm is not None:
-        cfg["ordered"] = True
-        ins = _deformation.permute_rows(perm, ins)
+def _deformer(pc):
+    """(perm, forward): forward(t) is the five arrays render()'s no-grad branch hands to the rasterizer at time t -- its cfg, its implicit
+    Hilbert permutation of the inputs (renderer._fine_stage), activate=True.  Call under torch.no_grad()."""
+    cfg, perm, ins, net_ins = _renderer._fine_stage(pc)
 
     def forward(t):
-        st = _deformation.forward_impl(cfg, t, *ins, None, dn.grid.aabb, (*planes, *mlp), False)
+        st = _deformation.forward_impl(cfg, t, *ins, None, net_ins[0], net_ins[1:], False)
         return (st.o_xyz, st.o_sc, st.o_rot, st.o_op, st.o_sh)
     return perm, forward
 
@@ -321,7 +315,7 @@ def _extent_pass(forward, ts, head_on, N, device):
     first.  Two states are alive at a time."""
     ref = forward(ts[0])
     ext = torch.zeros(N, len(FIELDS), dtype=torch.float32, device=device)
-    mask = sum(1 << h for h, on in enumerate(head_on) if on)
+    mask = _field_mask(head_on)
     for t in ts[1:]:
         cur = forward(t)
         _lib.check(_lib.lib().fdgs_state_extent(_lib.stream_ptr(), N, mask, _state_arrays(ref, mask), _state_arrays(cur, mask), _lib.ptr(ext)))
@@ -332,7 +326,7 @@ def _checked_model(pc, who):
     net = pc._deformation
     if not isinstance(net, _deformation.deform_network):
         raise TypeError(f"{who}: pc._deformation must be this package's deform_network")
-    return net, _deformation._head_on(net.deformation_net.args), int(pc._xyz.shape[0])
+    return _deformation._head_on(net.deformation_net.args), int(pc._xyz.shape[0])
 
 
 def motion_extent(pc, times):
@@ -342,9 +336,9 @@ def motion_extent(pc, times):
     with `tol`: a quantile of a column is the tolerance that keeps that share of the rows static.  One deformation forward per timestamp,
     exactly `bake`'s; two states of scratch, whatever len(times)."""
     ts = _checked_times(times)
-    net, head_on, N = _checked_model(pc, "motion_extent")
+    head_on, N = _checked_model(pc, "motion_extent")
     with torch.no_grad():
-        perm, forward = _deformer(pc, net, head_on)
+        perm, forward = _deformer(pc)
         _, ext = _extent_pass(forward, ts, head_on, N, pc._xyz.device)
         if perm is not None:
             ext, = _deformation.permute_rows(perm, [ext], scatter=True)
@@ -376,8 +370,11 @@ class SparseBaked:
         self.N, self.D = int(arrays[0].shape[0]), int(rows.shape[0])
         self.nbytes = 4 * (working.numel() + compact_storage.numel())
         self.launches = 0
-        self._mask = sum(1 << h for h, on in enumerate(self.head_on) if on)
+        self._mask = _field_mask(self.head_on)
         self._frame = BakedFrame(arrays)
+        # the fdgs_state_arrays of every timestamp's compact rows and of the working state: they never change, filled once
+        self._sources, self._target = [_state_arrays(c, self._mask) for c in compact], _state_arrays(arrays, self._mask)
+        self._maps = _perm_maps(perm)
         self._shown = (0, 0, 0.0)               # the (i, j, w) the dynamic rows of the working state hold
 
     @property
@@ -388,23 +385,20 @@ class SparseBaked:
         """(BakedFrame over the working state, (i, j, w)) for frame time t.  ONE fdgs_state_scatter launch (a copy of compact[i] at a baked
         timestamp or with interp="nearest", else the blend of compact[i] and compact[j] fused into it) when (i, j, w) is not what the
         working state holds; none when it is, when D == 0 or when no head is on.  The frame is overwritten by the next call."""
-        if interp not in ("linear", "nearest"):
-            raise ValueError(f"interp: 'linear' or 'nearest', not {interp!r}")
-        key = _locate(self.times, t, interp)
+        key = _locate(self.times, t, _checked_interp(interp))
         if self.D and self._mask and key != self._shown:
             i, j, w = key
             blend = i != j
-            a, b = _state_arrays(self._compact[i], self._mask), _state_arrays(self._compact[j], self._mask)
-            _lib.check(_lib.lib().fdgs_state_scatter(_lib.stream_ptr(), self.D, _lib.ptr(self.rows), self.N, self._mask, a, b if blend else None,
-                                                     float(w) if blend else 0.0, _state_arrays(self._frame.arrays(), self._mask)))
+            _lib.check(_lib.lib().fdgs_state_scatter(_lib.stream_ptr(), self.D, _lib.ptr(self.rows), self.N, self._mask, self._sources[i],
+                                                     self._sources[j] if blend else None, float(w) if blend else 0.0, self._target))
             self.launches += 1
             self._shown = key
         return self._frame, key
 
     def render(self, viewpoint_camera, pipe, bg_color, scaling_modifier=1.0, override_color=None, cam_type=None, interp="linear", rgb8=None):
         """The contract of `Baked.render`, on the state `state_at` gives."""
-        return _render_state(self, "SparseBaked.render", viewpoint_camera, pipe, bg_color, scaling_modifier, override_color, cam_type, interp,
-                             rgb8)
+        return _render_state("SparseBaked.render", lambda t: self.state_at(t, interp)[0], self.active_sh_degree, self.device,
+                             *self._maps, viewpoint_camera, pipe, bg_color, scaling_modifier, override_color, cam_type, rgb8)
 
 
 def bake_sparse(pc, times, tol, max_bytes=None):
@@ -419,21 +413,18 @@ def bake_sparse(pc, times, tol, max_bytes=None):
     again when the full state and the compact rows do."""
     ts = _checked_times(times)
     tol = _checked_tol(tol)
-    net, head_on, N = _checked_model(pc, "bake_sparse")
+    head_on, N = _checked_model(pc, "bake_sparse")
     T = len(ts)
     need = sparse_bake_bytes(N, 0, T, head_on)
     if max_bytes is not None and need > max_bytes:
         raise MemoryError(f"bake_sparse: the full state of {N} Gaussians needs {need} bytes, max_bytes = {max_bytes}")
     device = pc._xyz.device
     on = [h for h in range(len(FIELDS)) if head_on[h]]
-    mask = sum(1 << h for h in on)
+    mask = _field_mask(head_on)
     with torch.no_grad():
-        perm, forward = _deformer(pc, net, head_on)
-        working = torch.empty(need // 4, dtype=torch.float32, device=device)
-        arrays, off = [], 0
-        for w, shp in zip(FIELD_WIDTH, FIELD_SHAPE):
-            arrays.append(working[off:off + N * w].view(N, *shp))
-            off += _slot_floats(N, w)
+        perm, forward = _deformer(pc)
+        working = torch.empty(need // 4, dtype=torch.float32, device=device)          # (D = 0: the full state and nothing else)
+        arrays = [v[0] for v in _carve(_field_slots(N), working)[1]]
         first, ext = _extent_pass(forward, ts, head_on, N, device)
         for dst, src in zip(arrays, first):
             dst.copy_(src)
@@ -448,13 +439,9 @@ def bake_sparse(pc, times, tol, max_bytes=None):
         if max_bytes is not None and need > max_bytes:
             raise MemoryError(f"bake_sparse: {D} dynamic rows of {N} at {T} timestamps need {need} bytes, max_bytes = {max_bytes}")
         storage = torch.empty(need // 4 - working.numel(), dtype=torch.float32, device=device)
-        compact, off = [[None] * len(FIELDS) for _ in range(T)], 0
-        for h in on:
-            stride = _slot_floats(D, FIELD_WIDTH[h])
-            for k in range(T):
-                compact[k][h] = storage[off + k * stride:off + k * stride + D * FIELD_WIDTH[h]].view(D, *FIELD_SHAPE[h])
-            off += stride * T
-        rows = storage[off:off + D].view(torch.int32)
+        *per_field, (rows,) = _carve(_compact_slots(D, T, head_on), storage)[1]
+        compact = [[v[k] if v else None for v in per_field] for k in range(T)]
+        rows = rows.view(torch.int32)
         rows.copy_(found)
         if D and mask:
             for k, t in enumerate(ts):

@@ -44,10 +44,55 @@ def _implicit_perm(pc, cfg, dn):
     return None
 
 
+def _fine_stage(pc, lead=()):
+    """What the fused fine stage of one frame runs on -> (cfg, perm, per-Gaussian inputs, network inputs).  The inputs are `lead` (the
+    gradient sinks of the screen-space means) and the model's six arrays; where the set is read through the implicit Hilbert permutation
+    they are permuted here (gradients come back through the inverse; detached when no graph is recorded) and cfg["ordered"] is set.
+    render(), render_views() and the baked playback all deform through this, which is what keeps a baked frame render()'s own."""
+    net = pc._deformation
+    planes, mlp = _deformation._collect(net)
+    dn = net.deformation_net
+    cfg = _deformation._forward_cfg(dn, pc._xyz, True)
+    ins = (*lead, pc.get_xyz, pc._scaling, pc._rotation, pc._opacity, pc._features_dc, pc._features_rest)
+    perm = _implicit_perm(pc, cfg, dn)
+    if perm is not None:
+        cfg["ordered"] = True
+        ins = _deformation.PermuteRows.apply(perm, *ins) if cfg["grad"] else tuple(_deformation.permute_rows(perm, [t.detach() for t in ins]))
+    return cfg, perm, ins, (dn.grid.aabb, *planes, *mlp)
+
+
+def _frame_settings(camera, cam_type, bg_color, scaling_modifier, sh_degree, device, pipe):
+    """(GaussianRasterizationSettings, frame time) of one camera, as gaussian_renderer/__init__.py:31-58 builds them: a "PanopticSports"
+    camera is a dict that brings its settings along."""
+    if cam_type == "PanopticSports":
+        return camera["camera"], float(camera["time"])
+    return GaussianRasterizationSettings(
+        image_height=int(camera.image_height), image_width=int(camera.image_width), tanfovx=math.tan(camera.FoVx * 0.5),
+        tanfovy=math.tan(camera.FoVy * 0.5), bg=bg_color, scale_modifier=scaling_modifier,
+        viewmatrix=_dev(camera.world_view_transform, device), projmatrix=_dev(camera.full_proj_transform, device),
+        sh_degree=sh_degree, campos=_dev(camera.camera_center, device), prefiltered=False, debug=pipe.debug), float(camera.time)
+
+
 def _tile_flags():
     if EPILOGUE_TILE_FLAGS is not None:
         return int(EPILOGUE_TILE_FLAGS)
     return 2 if _lib.tuning_get("skip_dead") != 0 else 1
+
+
+def _fill_epilogue(st, b, assign):
+    """The fdgs_raster_deform_epilogue of one view's rasterizer backward: its per-Gaussian chain rule writes straight into the deformation
+    backward's buffers `b` (assign: the identity paths are assigned, not accumulated into)."""
+    epi = _lib.RasterDeformEpilogue()
+    epi.activate, epi.Npad = 1, (st.p.N + 127) // 128 * 128
+    epi.rot_norm, epi.G = _lib.ptr(st.o_norm), _lib.ptr(b.scratch)
+    epi.d_xyz, epi.d_scales, epi.d_rotations, epi.d_opacity = b.g.d_xyz, b.g.d_scales, b.g.d_rotations, b.g.d_opacity
+    epi.d_shs_dc, epi.d_shs_rest = b.g.d_shs_dc, b.g.d_shs_rest
+    epi.shs_dc_stride, epi.shs_rest_stride = st.p.shs_dc_stride, st.p.shs_rest_stride
+    epi.assign = 1 if assign else 0
+    epi.tile_flags = _tile_flags()      # per-tile non-zero flags behind the packed rows; 2: rows of dead tiles stay unwritten
+    if b.zero_range is not None:        # the accumulate-into part of the gradient arena is cleared by the epilogue kernel on the way
+        epi.zero_fill, epi.zero_floats = b.zero_range
+    return epi
 
 
 class _FusedRenderFunction(torch.autograd.Function):
@@ -84,16 +129,7 @@ class _FusedRenderFunction(torch.autograd.Function):
         g_means2D = torch.empty(P, 3, device=dev)
         acc, g.scratch_acc_zeroed = rstate.take_accumulator()       # (zero-filled by the blending forward of this frame: no fill launch here)
         g.dL_dcolor, g.dL_ddepth, g.dL_dmeans2D, g.scratch_acc = _lib.ptr(grad_color), _lib.ptr(grad_depth), _lib.ptr(g_means2D), _lib.ptr(acc)
-        epi = _lib.RasterDeformEpilogue()
-        epi.activate, epi.Npad = 1, (P + 127) // 128 * 128
-        epi.rot_norm, epi.G = _lib.ptr(st.o_norm), _lib.ptr(b.scratch)
-        epi.d_xyz, epi.d_scales, epi.d_rotations, epi.d_opacity = b.g.d_xyz, b.g.d_scales, b.g.d_rotations, b.g.d_opacity
-        epi.d_shs_dc, epi.d_shs_rest = b.g.d_shs_dc, b.g.d_shs_rest
-        epi.shs_dc_stride, epi.shs_rest_stride = st.p.shs_dc_stride, st.p.shs_rest_stride
-        epi.assign = 1 if EPILOGUE_ASSIGN else 0
-        epi.tile_flags = _tile_flags()      # per-tile non-zero flags behind the packed rows; 2: rows of dead tiles stay unwritten
-        if b.zero_range is not None:        # the accumulate-into part of the gradient arena is cleared by the epilogue kernel on the way
-            epi.zero_fill, epi.zero_floats = b.zero_range
+        epi = _fill_epilogue(st, b, EPILOGUE_ASSIGN)
         g.deform_epilogue = _lib.ctypes.pointer(epi)
         _lib.check(L.fdgs_raster_bwd(_lib.stream_ptr(), p, _lib.ptr(rstate.geom), _lib.ptr(rstate.binning), _lib.ptr(rstate.img),
                                      rstate.capacity, g))
@@ -159,14 +195,7 @@ class _FusedRenderViewsFunction(torch.autograd.Function):
             gm = torch.empty(P, 3, device=dev)
             acc, g.scratch_acc_zeroed = rstate.take_accumulator()
             g.dL_dcolor, g.dL_ddepth, g.dL_dmeans2D, g.scratch_acc = _lib.ptr(gc), _lib.ptr(gd), _lib.ptr(gm), _lib.ptr(acc)
-            epi = _lib.RasterDeformEpilogue()
-            epi.activate, epi.Npad = 1, (P + 127) // 128 * 128
-            epi.rot_norm, epi.G = _lib.ptr(st.o_norm), _lib.ptr(b.scratch)
-            epi.d_xyz, epi.d_scales, epi.d_rotations, epi.d_opacity = b.g.d_xyz, b.g.d_scales, b.g.d_rotations, b.g.d_opacity
-            epi.d_shs_dc, epi.d_shs_rest = b.g.d_shs_dc, b.g.d_shs_rest
-            epi.shs_dc_stride, epi.shs_rest_stride = st.p.shs_dc_stride, st.p.shs_rest_stride
-            epi.assign = 1 if (EPILOGUE_ASSIGN and k_ == 0) else 0       # later views accumulate into what the first processed one assigned
-            epi.tile_flags = _tile_flags()
+            epi = _fill_epilogue(st, b, EPILOGUE_ASSIGN and k_ == 0)      # later views accumulate into what the first processed one assigned
             g.deform_epilogue = _lib.ctypes.pointer(epi)
             _lib.check(L.fdgs_raster_bwd(_lib.stream_ptr(), p, _lib.ptr(rstate.geom), _lib.ptr(rstate.binning), _lib.ptr(rstate.img),
                                          rstate.capacity, g))
@@ -198,33 +227,12 @@ def render_views(viewpoint_cameras, pc, pipe, bg_color, scaling_modifier=1.0, st
         return [render(c, pc, pipe, bg_color, scaling_modifier, None, stage, cam_type) for c in cams]
     means3D = pc.get_xyz
     device = means3D.device
-    settings, times = [], []
-    for cam in cams:
-        if cam_type != "PanopticSports":
-            settings.append(GaussianRasterizationSettings(
-                image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
-                tanfovy=math.tan(cam.FoVy * 0.5), bg=bg_color, scale_modifier=scaling_modifier,
-                viewmatrix=_dev(cam.world_view_transform, device), projmatrix=_dev(cam.full_proj_transform, device),
-                sh_degree=pc.active_sh_degree, campos=_dev(cam.camera_center, device), prefiltered=False, debug=pipe.debug))
-            times.append(float(cam.time))
-        else:
-            settings.append(cam["camera"])
-            times.append(float(cam["time"]))
+    settings, times = zip(*[_frame_settings(cam, cam_type, bg_color, scaling_modifier, pc.active_sh_degree, device, pipe) for cam in cams])
     if len({(s_.image_height, s_.image_width) for s_ in settings}) != 1:
         return [render(c, pc, pipe, bg_color, scaling_modifier, None, stage, cam_type) for c in cams]
     sinks = [_zero_leaf(means3D) for _ in cams]
-    net = pc._deformation
-    planes, mlp = _deformation._collect(net)
-    dn = net.deformation_net
-    cfg = dict(C=dn.grid.grid_config[0]["output_coordinate_dim"], L=len(dn.grid.grids), W=dn.W, head_on=_deformation._head_on(dn.args),
-               activate=True, save=bool(_deformation.SAVE_ACTIVATIONS and torch.is_grad_enabled()), grad=torch.is_grad_enabled(),
-               ordered=_deformation.spatial_order_hint(pc._xyz))
-    perm = _implicit_perm(pc, cfg, dn)
-    ins = (*sinks, means3D, pc._scaling, pc._rotation, pc._opacity, pc._features_dc, pc._features_rest)
-    if perm is not None:       # the set in Hilbert order for this step (gradients come back through the inverse)
-        cfg["ordered"] = True
-        ins = _deformation.PermuteRows.apply(perm, *ins) if cfg["grad"] else tuple(_deformation.permute_rows(perm, [t.detach() for t in ins]))
-    colors, radii, depths = _FusedRenderViewsFunction.apply(cfg, times, settings, len(cams), *ins, dn.grid.aabb, *planes, *mlp)
+    cfg, perm, ins, net_ins = _fine_stage(pc, sinks)       # (the set in Hilbert order for this step where perm is not None)
+    colors, radii, depths = _FusedRenderViewsFunction.apply(cfg, times, settings, len(cams), *ins, *net_ins)
     if perm is not None:
         radii = torch.stack(_deformation.permute_rows(perm, [radii[v] for v in range(len(cams))], scatter=True))
     return [{"render": colors[v], "viewspace_points": sinks[v], "visibility_filter": radii[v] > 0, "radii": radii[v], "depth": depths[v]}
@@ -265,19 +273,25 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     # `zeros_like(...) + 0` with retain_grad() costs an extra add kernel per frame plus a clone of the gradient in the retain hook;
     # a leaf's .grad is filled by AccumulateGrad directly (same values, same attribute, read the same way by the train loop)
     screenspace_points = _zero_leaf(means3D)
-    if cam_type != "PanopticSports":
-        tanfovx = math.tan(viewpoint_camera.FoVx * 0.5)
-        tanfovy = math.tan(viewpoint_camera.FoVy * 0.5)
-        raster_settings = GaussianRasterizationSettings(
-            image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
-            tanfovx=tanfovx, tanfovy=tanfovy, bg=bg_color, scale_modifier=scaling_modifier,
-            viewmatrix=_dev(viewpoint_camera.world_view_transform, device),
-            projmatrix=_dev(viewpoint_camera.full_proj_transform, device), sh_degree=pc.active_sh_degree,
-            campos=_dev(viewpoint_camera.camera_center, device), prefiltered=False, debug=pipe.debug)
-        frame_time = float(viewpoint_camera.time)
-    else:
-        raster_settings = viewpoint_camera["camera"]
-        frame_time = float(viewpoint_camera["time"])
+    raster_settings, frame_time = _frame_settings(viewpoint_camera, cam_type, bg_color, scaling_modifier, pc.active_sh_degree, device, pipe)
+    if ("fine" in stage and "coarse" not in stage and FUSED_BACKWARD and override_color is None and not pipe.compute_cov3D_python
+            and not pipe.convert_SHs_python and isinstance(pc._deformation, _deformation.deform_network)):
+        # deformation + rasterizer as one autograd node (see _FusedRenderFunction)
+        cfg, perm, ins, net_ins = _fine_stage(pc, (screenspace_points,) if torch.is_grad_enabled() else ())
+        if cfg["grad"]:
+            rendered_image, radii, depth, vis = _FusedRenderFunction.apply(cfg, frame_time, raster_settings, *ins, *net_ins)
+        else:
+            # no graph will be recorded (render.py:57-70, evaluation): the two stages called directly -- autograd.Function.apply costs
+            # 0.05 ms per frame for its 46 inputs even when it has nothing to record
+            st = _deformation.forward_impl(cfg, frame_time, *ins, None, net_ins[0], net_ins[1:], False)
+            rendered_image, radii, depth, rstate = _rasterizer.rasterize_forward(raster_settings, st.o_xyz, st.o_sh, None, st.o_op, st.o_sc,
+                                                                                 st.o_rot, None, expect_backward=False)
+            vis = rstate.visibility
+        if perm is not None:       # (radii and visibility back in the model's own row order)
+            radii, = _deformation.permute_rows(perm, [radii], scatter=True)
+            vis = radii > 0
+        return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": vis, "radii": radii, "depth": depth}
+
     means2D = screenspace_points
     opacity = pc._opacity
     scales = rotations = cov3D_precomp = None
@@ -293,47 +307,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         rotations_final = None if rotations is None else pc.rotation_activation(rotations)
         opacity_final = pc.opacity_activation(opacity)
     elif "fine" in stage:
-        if fused and FUSED_BACKWARD and override_color is None and not pipe.convert_SHs_python:
-            # deformation + rasterizer as one autograd node (see _FusedRenderFunction)
-            net = pc._deformation
-            planes, mlp = _deformation._collect(net)
-            dn = net.deformation_net
-            cfg = dict(C=dn.grid.grid_config[0]["output_coordinate_dim"], L=len(dn.grid.grids), W=dn.W,
-                       head_on=_deformation._head_on(dn.args), activate=True,
-                       save=bool(_deformation.SAVE_ACTIVATIONS and torch.is_grad_enabled()), grad=torch.is_grad_enabled(),
-                       ordered=_deformation.spatial_order_hint(pc._xyz))
-            perm = _implicit_perm(pc, cfg, dn)
-            f_dc, f_rest = pc._features_dc, pc._features_rest
-            if perm is not None:       # the set in Hilbert order for this frame (gradients come back through the inverse)
-                cfg["ordered"] = True
-                if cfg["grad"]:
-                    means2D, means3D, scales, rotations, opacity, f_dc, f_rest = _deformation.PermuteRows.apply(
-                        perm, means2D, means3D, scales, rotations, opacity, f_dc, f_rest)
-                else:
-                    means3D, scales, rotations, opacity, f_dc, f_rest = _deformation.permute_rows(
-                        perm, [t.detach() for t in (means3D, scales, rotations, opacity, f_dc, f_rest)])
-            if not cfg["grad"]:
-                # no graph will be recorded (render.py:57-70, evaluation): the two stages called directly -- autograd.Function.apply costs
-                # 0.05 ms per frame for its 46 inputs even when it has nothing to record
-                st = _deformation.forward_impl(cfg, frame_time, means3D, scales, rotations, opacity, f_dc, f_rest,
-                                               None, dn.grid.aabb, (*planes, *mlp), False)
-                rendered_image, radii, depth, rstate = _rasterizer.rasterize_forward(raster_settings, st.o_xyz, st.o_sh, None, st.o_op, st.o_sc,
-                                                                                     st.o_rot, None, expect_backward=False)
-                vis = rstate.visibility
-                if perm is not None:
-                    radii, = _deformation.permute_rows(perm, [radii], scatter=True)
-                    vis = radii > 0
-                return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": vis,
-                        "radii": radii, "depth": depth}
-            rendered_image, radii, depth, vis = _FusedRenderFunction.apply(
-                cfg, frame_time, raster_settings, means2D, means3D, scales, rotations, opacity, f_dc, f_rest,
-                dn.grid.aabb, *planes, *mlp)
-            if perm is not None:
-                radii, = _deformation.permute_rows(perm, [radii], scatter=True)
-                vis = radii > 0
-            return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": vis,
-                    "radii": radii, "depth": depth}
-        elif fused:
+        if fused:
             means3D_final, scales_final, rotations_final, opacity_final, shs_final = _deformation.deform(
                 pc._deformation, means3D, scales, rotations, opacity, shs_dc=pc._features_dc, shs_rest=pc._features_rest,
                 time=frame_time, activate=True)

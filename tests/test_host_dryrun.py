@@ -15,6 +15,8 @@ syn = fdgs.synthetic
 class _FakeLib:
     def __init__(self):
         self.calls = []
+        self.record = False         # True: keep the non-pointer struct fields of the calls below (the front-end tests)
+        self.deform, self.raster, self.epilogue = [], [], []
 
     def __getattr__(self, name):
         if not name.startswith("fdgs_"):
@@ -22,6 +24,8 @@ class _FakeLib:
 
         def fn(*a):
             self.calls.append(name)
+            if self.record:
+                self._note(name, a)
             if name in ("fdgs_geom_bytes", "fdgs_img_bytes", "fdgs_binning_bytes", "fdgs_deform_saved_bytes", "fdgs_deform_bwd_scratch_bytes"):
                 a[-1].value = 4096
             elif name == "fdgs_bin_prepare":
@@ -43,6 +47,20 @@ class _FakeLib:
             return 0
         return fn
 
+    def _note(self, name, a):
+        if name == "fdgs_deform_fwd":
+            p, out = a[1], a[2]
+            self.deform.append(dict(N=p.N, C=p.C, L=p.L, W=p.W, head_on=list(p.head_on), activate=p.activate, shs_dc_stride=p.shs_dc_stride,
+                                    shs_rest_stride=p.shs_rest_stride, time_scalar=p.time_scalar, saved_null=not out.saved,
+                                    rot_norm_null=not out.rot_norm))
+        elif name in ("fdgs_preprocess_fwd", "fdgs_raster_fwd_capacity"):
+            p = a[1]
+            self.raster.append({k: getattr(p, k) for k in ("P", "sh_degree", "sh_coeffs", "W", "H", "tanfovx", "tanfovy", "scale_modifier",
+                                                           "prefiltered", "debug")})
+        elif name == "fdgs_raster_bwd" and a[6].deform_epilogue:
+            e = a[6].deform_epilogue.contents
+            self.epilogue.append((e.assign, e.tile_flags, e.activate, e.Npad, e.zero_floats))
+
 
 @pytest.fixture
 def fake(monkeypatch):
@@ -55,6 +73,7 @@ def fake(monkeypatch):
     monkeypatch.setattr(fdgs.rasterizer, "_current_stream", lambda dev: type("S", (), {"synchronize": lambda self: None})())
     monkeypatch.setattr(fdgs.rasterizer, "_tls", __import__("threading").local())
     monkeypatch.setattr(fdgs.rasterizer, "_seen", {})
+    monkeypatch.setattr(fdgs.rasterizer, "_size_cache", {})
     # rasterize_forward / forward_impl refuse non-HIP tensors: the dry run claims to be one
     monkeypatch.setattr(fdgs.rasterizer, "_is_hip_device", lambda dev: True)
     monkeypatch.setattr(fdgs.deformation, "_is_hip_device", lambda dev: True)
@@ -199,3 +218,221 @@ def test_host_time_per_frame_stays_within_budget(fake):
         best = min(best, (time.perf_counter() - t0) / 100 * 1e3)
     print(f"host time per render() forward + backward: {best:.3f} ms")
     assert best < 1.7, best
+
+
+# ---- the frame front end: what render, render_views, playback and compose hand to the library ---------------------------------------------
+# Every literal below was recorded at the commit BEFORE render / render_views / bake / Baked.render / Composite.render came to share one
+# camera block, one deformation plan, one render body and one slot layout: they pin that commit's behaviour.  N = 300 takes the models'
+# own row order, N = 8200 (>= renderer.IMPLICIT_ORDER_MIN_N, a random cube) the implicit Hilbert permutation.
+
+P, C = fdgs.playback, fdgs.compose
+TIMES = (0.0, 0.5, 1.0)
+SIZES = (300, 8200)
+
+
+def _model(n, cfg="dynerf_default", seed=1):
+    return syn.SynthModel(n, cfg, seed=seed)
+
+
+def _cam(t=0.5, theta=10.0):
+    return syn.make_camera(64, 48, theta_deg=theta, time=t)
+
+
+def _colors(n):
+    return torch.rand(n, 3, generator=torch.Generator().manual_seed(4))
+
+
+def _run_bake(fake, n):
+    pc = _model(n)
+    fake.calls.clear()
+    P.bake(pc, TIMES)
+
+
+def _run_baked_render(fake, n):
+    baked = P.bake(_model(n), TIMES)
+    fake.calls.clear()
+    out = baked.render(_cam(0.5), _Pipe(), torch.zeros(3), rgb8="trunc")
+    assert out["rgb8"].shape == (48, 64, 3) and out["viewspace_points"] is None
+    fake.calls.append("fdgs_--")
+    out = baked.render(_cam(0.25), _Pipe(), torch.zeros(3), override_color=_colors(n))
+    assert out["radii"].shape == (n,) and out["visibility_filter"].dtype == torch.bool
+
+
+def _run_bake_sparse(fake, n):
+    pc = _model(n)
+    fake.calls.clear()
+    sb = P.bake_sparse(pc, TIMES, tol=-1.0)
+    assert sb.D == n and sb.nbytes == P.sparse_bake_bytes(n, n, len(TIMES), sb.head_on)
+
+
+def _run_sparse_render(fake, n):
+    sb = P.bake_sparse(_model(n), TIMES, tol=-1.0)
+    fake.calls.clear()
+    sb.render(_cam(0.5), _Pipe(), torch.zeros(3), rgb8="round")
+    fake.calls.append("fdgs_--")
+    out = sb.render(_cam(0.25), _Pipe(), torch.zeros(3), override_color=_colors(n))
+    assert out["radii"].shape == (n,) and sb.launches == 2
+
+
+def _run_motion_extent(fake, n):
+    pc = _model(n)
+    fake.calls.clear()
+    assert P.motion_extent(pc, TIMES).shape == (n, 5)
+
+
+def _two_baked(n):
+    return [P.bake(_model(n, seed=1), TIMES), P.bake(_model(n, "dnerf_bouncingballs", seed=2), TIMES)]
+
+
+def _run_compose(fake, n):
+    models = _two_baked(n)
+    fake.calls.clear()
+    scene = C.compose(models, [None, C.Placement(rotation=(0.0, 1.0, 0.0, 0.0), translation=(0.5, 0.0, -0.25), scale=0.5)])
+    assert scene.N == 2 * n and scene.nbytes == C.compose_bytes([n, n])
+
+
+def _run_composite_render(fake, n):
+    scene = C.compose(_two_baked(n), [None, C.Placement(translation=(0.5, 0.0, -0.25), scale=0.5, time_offset=0.1)])
+    fake.calls.clear()
+    scene.render(_cam(0.5), _Pipe(), torch.zeros(3), rgb8="trunc")
+    fake.calls.append("fdgs_--")
+    out = scene.render(_cam(0.25), _Pipe(), torch.zeros(3), override_color=_colors(2 * n))
+    assert out["radii"].shape == (2 * n,) and out["viewspace_points"] is None
+
+
+def _run_render_nograd(fake, n):
+    pc = _model(n)
+    fake.calls.clear()
+    with torch.no_grad():
+        fdgs.render(_cam(0.5), pc, _Pipe(), torch.zeros(3), stage="fine")
+        fake.calls.append("fdgs_--")
+        fdgs.render(_cam(0.25), pc, _Pipe(), torch.zeros(3), stage="fine")
+
+
+def _run_render_backward(fake, n):
+    pc = _model(n)
+    fake.calls.clear()
+    res = fdgs.render(_cam(0.5), pc, _Pipe(), torch.zeros(3), stage="fine")
+    res["render"].sum().backward()
+    assert pc._xyz.grad.shape == (n, 3) and res["viewspace_points"].grad.shape == (n, 3)
+
+
+def _run_render_views(fake, n):
+    pc = _model(n, "dnerf_bouncingballs", seed=2)
+    fake.calls.clear()
+    res = fdgs.render_views([_cam(0.1 * i, 10.0 * i) for i in range(3)], pc, _Pipe(), torch.zeros(3), stage="fine")
+    sum(r["render"].sum() for r in res).backward()
+    assert all(r["viewspace_points"].grad.shape == (n, 3) and r["radii"].shape == (n,) for r in res)
+
+
+_RUNS = dict(bake=_run_bake, baked_render=_run_baked_render, bake_sparse=_run_bake_sparse, sparse_render=_run_sparse_render,
+             motion_extent=_run_motion_extent, compose=_run_compose, composite_render=_run_composite_render,
+             render_nograd=_run_render_nograd, render_backward=_run_render_backward, render_views=_run_render_views)
+
+
+def _calls_of(fake, entry, n):
+    """The ordered fdgs_* calls of one entry point, prefix dropped; "--" separates two calls of it."""
+    _RUNS[entry](fake, n)
+    return " ".join(c[len("fdgs_"):] for c in fake.calls)
+
+
+_FWD = "deform_pack_bytes deform_fwd"
+_EXACT = "geom_bytes img_bytes preprocess_fwd bin_prepare binning_bytes bin_sort render_fwd"
+_CAP = "binning_bytes raster_fwd_capacity pair_count_wait"
+_BWD = "tuning_get raster_bwd deform_bwd"
+PARENT_CALLS = {
+    ('bake', 300): f"{_FWD} {_FWD} {_FWD}",
+    ('bake', 8200): f"permute_rows {_FWD} {_FWD} {_FWD}",
+    ('bake_sparse', 300): f"{_FWD} {_FWD} state_extent {_FWD} state_extent {_FWD} state_gather {_FWD} state_gather {_FWD} state_gather",
+    ('bake_sparse', 8200): f"permute_rows {_FWD} {_FWD} state_extent {_FWD} state_extent {_FWD} state_gather {_FWD} state_gather {_FWD} state_gather permute_rows",
+    ('baked_render', 300): f"{_EXACT} image_rgb8 -- state_blend {_CAP}",
+    ('baked_render', 8200): f"{_EXACT} permute_rows image_rgb8 -- state_blend permute_rows {_CAP} permute_rows",
+    ('compose', 300): f"state_place",
+    ('compose', 8200): f"state_place",
+    ('composite_render', 300): f"state_place state_place {_EXACT} image_rgb8 -- state_place state_place {_CAP}",
+    ('composite_render', 8200): f"state_place state_place {_EXACT} permute_rows permute_rows image_rgb8 -- state_place state_place permute_rows permute_rows {_CAP} permute_rows permute_rows",
+    ('motion_extent', 300): f"{_FWD} {_FWD} state_extent {_FWD} state_extent",
+    ('motion_extent', 8200): f"permute_rows {_FWD} {_FWD} state_extent {_FWD} state_extent permute_rows",
+    ('render_backward', 300): f"deform_saved_bytes {_FWD} {_EXACT} deform_bwd_scratch_bytes {_BWD}",
+    ('render_backward', 8200): f"permute_rows deform_saved_bytes {_FWD} {_EXACT} permute_rows deform_bwd_scratch_bytes {_BWD} permute_rows",
+    ('render_nograd', 300): f"{_FWD} {_EXACT} -- {_FWD} {_CAP}",
+    ('render_nograd', 8200): f"permute_rows {_FWD} {_EXACT} permute_rows -- permute_rows {_FWD} {_CAP} permute_rows",
+    ('render_views', 300): f"deform_saved_bytes {_FWD} {_EXACT} deform_saved_bytes {_FWD} {_CAP} deform_saved_bytes {_FWD} raster_fwd_capacity pair_count_wait deform_bwd_scratch_bytes {_BWD} {_BWD} {_BWD}",
+    ('render_views', 8200): f"permute_rows permute_rows deform_saved_bytes {_FWD} {_EXACT} deform_saved_bytes {_FWD} {_CAP} deform_saved_bytes {_FWD} raster_fwd_capacity pair_count_wait permute_rows deform_bwd_scratch_bytes {_BWD} {_BWD} {_BWD} permute_rows permute_rows",
+    ('sparse_render', 300): f"state_scatter {_EXACT} image_rgb8 -- state_scatter {_CAP}",
+    ('sparse_render', 8200): f"state_scatter {_EXACT} permute_rows image_rgb8 -- state_scatter permute_rows {_CAP} permute_rows",
+}
+
+
+PARENT_DEFORM_RECORD = {"N": 300, "C": 16, "L": 2, "W": 128, "head_on": [1, 1, 1, 1, 1], "activate": 1, "shs_dc_stride": 3, "shs_rest_stride": 45, "time_scalar": 0.5, "saved_null": True, "rot_norm_null": False}
+PARENT_RASTER_RECORD = {
+    False: {"P": 300, "sh_degree": 3, "sh_coeffs": 16, "W": 64, "H": 48, "tanfovx": 0.36000001430511475, "tanfovy": 0.27000001072883606, "scale_modifier": 0.75, "prefiltered": 0, "debug": 0},
+    True: {"P": 300, "sh_degree": 2, "sh_coeffs": 16, "W": 56, "H": 40, "tanfovx": 0.44999998807907104, "tanfovy": 0.30000001192092896, "scale_modifier": 0.75, "prefiltered": 0, "debug": 1},
+}
+PARENT_EPILOGUE_RENDER = [(1, 1, 1, 384, 2460096)]
+PARENT_EPILOGUE_VIEWS = [(1, 1, 1, 384, 0), (0, 1, 1, 384, 0), (0, 1, 1, 384, 0)]
+
+
+@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("entry", sorted(_RUNS))
+def test_entry_points_make_the_calls_they_made_before_the_front_end_was_shared(fake, entry, n):
+    assert _calls_of(fake, entry, n) == PARENT_CALLS[entry, n]
+
+
+@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("cfg", ["dynerf_default", "dnerf_bouncingballs", "hypernerf_default"])
+def test_bake_bake_sparse_and_motion_extent_deform_exactly_as_render_does_without_grad(fake, cfg, n):
+    """The bit-equality of baked playback with fdgs.render under torch.no_grad() rests on this: at one time value every entry point fills
+    the same fdgs_deform_params and asks for neither saved activations nor (activate being on) a missing rot_norm."""
+    fake.record = True
+    pc = _model(n, cfg, seed=3)
+
+    def records(run):
+        fake.deform.clear()
+        run()
+        return list(fake.deform)
+
+    def live():
+        with torch.no_grad():
+            for t in TIMES:
+                fdgs.render(_cam(t), pc, _Pipe(), torch.zeros(3), stage="fine")
+
+    want = records(live)
+    assert [r["time_scalar"] for r in want] == list(TIMES) and all(r["N"] == n and r["saved_null"] and not r["rot_norm_null"] for r in want)
+    assert records(lambda: P.bake(pc, TIMES)) == want
+    assert records(lambda: P.motion_extent(pc, TIMES)) == want
+    assert records(lambda: P.bake_sparse(pc, TIMES, tol=-1.0)) == want + want          # the extent pass, then the gather pass
+    if cfg == "dynerf_default":
+        assert want[1] == PARENT_DEFORM_RECORD | {"N": n}
+
+
+@pytest.mark.parametrize("panoptic", [False, True])
+def test_render_baked_render_and_composite_render_hand_the_rasterizer_the_same_settings(fake, panoptic):
+    fake.record = True
+    pc = _model(300)
+    bg, pipe = torch.tensor([0.1, 0.2, 0.3]), _Pipe()
+    cam, kw = _cam(0.5), {}
+    if panoptic:
+        settings = fdgs.rasterizer.GaussianRasterizationSettings(
+            image_height=40, image_width=56, tanfovx=0.45, tanfovy=0.3, bg=bg, scale_modifier=0.75, viewmatrix=cam.world_view_transform,
+            projmatrix=cam.full_proj_transform, sh_degree=2, campos=cam.camera_center, prefiltered=False, debug=True)
+        cam, kw = {"camera": settings, "time": 0.5}, {"cam_type": "PanopticSports"}
+    with torch.no_grad():
+        fdgs.render(cam, pc, pipe, bg, 0.75, stage="fine", **kw)
+    baked = P.bake(pc, TIMES)
+    baked.render(cam, pipe, bg, 0.75, **kw)
+    C.compose([baked]).render(cam, pipe, bg, 0.75, **kw)
+    live, from_baked, from_scene = fake.raster
+    assert live == from_baked == from_scene == PARENT_RASTER_RECORD[panoptic]
+    assert fake.deform[0]["time_scalar"] == 0.5
+
+
+def test_fused_backwards_fill_the_epilogue_as_before(fake):
+    """(assign, tile_flags, activate, Npad, zero_floats) of fdgs_raster_deform_epilogue: the single-view backward assigns and has the kernel
+    clear the rest of the arena; of three views behind one node only the first processed one assigns, and none clears."""
+    fake.record = True
+    _run_render_backward(fake, 300)
+    assert fake.epilogue == PARENT_EPILOGUE_RENDER
+    fake.epilogue.clear()
+    _run_render_views(fake, 300)
+    assert fake.epilogue == PARENT_EPILOGUE_VIEWS and [e[0] for e in fake.epilogue] == [1, 0, 0]
