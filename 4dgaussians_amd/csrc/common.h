@@ -54,8 +54,8 @@ constexpr int WAVE = 64;
 // only through fdgs_tuning_set() -- no C-ABI call reads the environment.  Everything else that used to be an FDGS_* variable is a constant
 // at its point of use (the tuned value; the sweeps are in profiles/r01b_tuning_sweep.txt).  Documented in INTEGRATION.md.
 struct Tuning {
-    int d1_form;     // FDGS_D1_FORM     0 (default: by shape, 8 at net_width 128 with up to two HexPlane levels, else 16) | 8 ( the weight-stationary form, deform_fwd_ws.h, where it applies) | 16 (deform_fwd16_kernel) | 32 (deform_fwd_kernel)
-    int d1_wgs;      // FDGS_D1_WGS      workgroups of the forward kernel; -1 = two (form 16) / one (form 32) per CU, 0 = one per four tiles
+    int d1_form;     // FDGS_D1_FORM     0 (default: by shape, 8 at net_width 128 with up to two HexPlane levels, else 16) | 8 (the weight-stationary form, deform_fwd_ws.h) | 16 (deform_fwd16_kernel) | 32 (deform_fwd_kernel); a form without an instance for the shape, or without the scratch it needs, gives way to the next (deform.hip: plan_fwd)
+    int d1_wgs;      // FDGS_D1_WGS      workgroups of the forward kernel; -1 = per CU: two (form 16; form 8 at net_width 64) / one (form 32; form 8 at net_width 128); > 0 = that many; 0 = one per 128 Gaussians (forms 16 / 32), as -1 (form 8)
     int d1_split;    // FDGS_D1_SPLIT    1 = the leftover tiles of the persistent loop are split by head over the waves
     int skip_dead;   // FDGS_SKIP_DEAD   1 = the deformation backward skips tiles without a gradient row (modes 0 / 2 of packed_rows_ready)
     int d4_mfma;     // FDGS_D4_MFMA     -1 = the caller's order hint picks the plane-gradient kernel, 1 / 0 force the splat / the per-corner form
@@ -74,6 +74,15 @@ inline int current_device_slot() {
     int d = 0;
     if (hipGetDevice(&d) != hipSuccess || d < 0) d = 0;
     return d % FDGS_MAX_DEVICES;
+}
+
+// compute units of the current device, asked once per device; 256 (MI355X) when the runtime cannot tell
+inline int device_cus() {
+    static int cus_of[FDGS_MAX_DEVICES] = {};
+    int& cus = cus_of[current_device_slot()];
+    int dev = 0;
+    if (cus == 0 && (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)) cus = 256;
+    return cus;
 }
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
