@@ -138,6 +138,8 @@ SYMBOLS = {
     "fdgs_deform_bwd_scratch_bytes": (c_int, [POINTER(DeformParams), POINTER(c_size_t)]),
     "fdgs_deform_bwd": (c_int, [c_void_p, POINTER(DeformParams), POINTER(DeformGrads)]),
     "fdgs_deform_bwd_live_tiles": (c_int, [c_void_p, POINTER(DeformParams), c_void_p, POINTER(c_uint32)]),
+    "fdgs_hexplane_cells": (c_int, [c_void_p, POINTER(DeformParams), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fdgs_hexplane_cells_host": (c_int, [POINTER(DeformParams), c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdgs_l1_stats": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
     "fdgs_l1_stats_scratch_bytes": (c_int, [POINTER(c_size_t)]),
     "fdgs_l1_stats_assign": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),

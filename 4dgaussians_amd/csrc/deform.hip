@@ -29,11 +29,12 @@
 //      over after the last full round of its persistent loop out by head (FDGS_D1_SPLIT).
 // This file is the host side only: validation, the layouts of the caller's buffers, one launch plan per pass and the C ABI.  The kernels are
 // the headers included below: deform_layers.h (MFMA wrappers, HexPlane sampling, DeformDev, the dense-layer blocks), deform_fwd32.h / _fwd16.h /
-// _fwd_ws.h (D1, three forms), deform_bwd_lists.h (prep, tile / row lists), deform_bwd32.h / _bwd_ws.h (D2), deform_wgrad.h (D3), deform_plane_grad.h (D4).
+// _fwd_ws.h (D1, three forms), hexplane_ops.h (the index arithmetic of the HexPlane lookup, host/device, contraction off), deform_bwd_lists.h (prep, tile / row lists), deform_bwd32.h / _bwd_ws.h (D2), deform_wgrad.h (D3), deform_plane_grad.h (D4).
 // Knobs (development / A-B only; the table is in api.hip, the struct in common.h, the defaults are the tuned values): d1_form, d1_wgs,
 // d1_split, skip_dead, row_compact, d2_form, d4_mfma, d4_rows_kb.  Build flags: -DFDGS_PROFILE_D1 / _WS / _D2 / _D2WS / _D4 add an in-kernel
 // s_memtime phase profile of one kernel (printed once to stderr); -DFDGS_DEV_ONLY_44 builds only the (128, 32) instance.
 #include "common.h"
+#include "hexplane_ops.h"
 
 #include <vector>
 
@@ -568,6 +569,26 @@ static int bwd_plane_grads(hipStream_t stream, const fdgs_deform_params* p, cons
                              raised[1][p->C == 32], blocks, PG_THREADS, lds_bytes, ga);
 }
 
+// ------------------------------------------------------------------------------------------------ probe of the HexPlane index arithmetic
+struct CellsArgs { fdgs_deform_params p; AabbScale sc; int32_t* cells; float *w1, *dscale, *q; };
+// one thread per Gaussian, plain vector stores; never on the frame path (tests/test_gpu_hexplane_cells.py compares it with the host twin)
+__global__ void __launch_bounds__(256) hexplane_cells_kernel(CellsArgs a) {
+    const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (n >= a.p.N) return;
+    const size_t per = (size_t)a.p.L * 4;
+    hexplane_cells_row(a.p, a.sc.inv2, (size_t)n, a.cells + (size_t)n * per * 2, a.w1 + (size_t)n * per, a.dscale + (size_t)n * per, a.q + (size_t)n * 4);
+}
+static int validate_cells(const fdgs_deform_params* p, const void* cells, const void* w1, const void* dscale, const void* q) {
+    FDGS_REQUIRE(p != nullptr, "params is NULL");
+    FDGS_REQUIRE(p->N >= 0, "N < 0");
+    FDGS_REQUIRE(p->L >= 1 && p->L <= FDGS_MAX_LEVELS, "1 <= len(multires) <= 4");
+    for (int l = 0; l < p->L; l++)
+        for (int i = 0; i < 4; i++) FDGS_REQUIRE(p->res[l][i] >= 2 && p->res[l][i] <= 4096, "plane resolution must be in [2, 4096]");
+    for (int i = 0; i < 3; i++) FDGS_REQUIRE(p->aabb[3 + i] != p->aabb[i], "degenerate aabb");
+    if (p->N > 0) FDGS_REQUIRE(p->xyz && cells && w1 && dscale && q, "NULL pointer");
+    return FDGS_OK;
+}
+
 }  // namespace fdgs
 
 using namespace fdgs;
@@ -678,4 +699,25 @@ extern "C" int fdgs_deform_bwd(void* stream_, const fdgs_deform_params* p, const
     if ((rc = bwd_data(stream, p, g, s))) return rc;
     if ((rc = bwd_wgrad(stream, p, g, s))) return rc;
     return bwd_plane_grads(stream, p, g, s, splat, Gc);
+}
+
+extern "C" int fdgs_hexplane_cells(void* stream_, const fdgs_deform_params* p, int32_t* cells, float* w1, float* dscale, float* q) {
+    int rc = validate_cells(p, cells, w1, dscale, q);
+    if (rc) return rc;
+    if (p->N == 0) return FDGS_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    CellsArgs a{};
+    a.p = *p; a.sc = aabb_scale(p); a.cells = cells; a.w1 = w1; a.dscale = dscale; a.q = q;
+    hipLaunchKernelGGL(hexplane_cells_kernel, dim3(cdiv(p->N, 256)), dim3(256), 0, stream, a);
+    FDGS_LAUNCH_CHECK("hexplane_cells_kernel", false, stream);
+    return FDGS_OK;
+}
+
+extern "C" int fdgs_hexplane_cells_host(const fdgs_deform_params* p, int32_t* cells, float* w1, float* dscale, float* q) {
+    int rc = validate_cells(p, cells, w1, dscale, q);
+    if (rc) return rc;
+    const AabbScale sc = aabb_scale(p);
+    const size_t per = (size_t)p->L * 4;
+    for (size_t n = 0; n < (size_t)p->N; n++) hexplane_cells_row(*p, sc.inv2, n, cells + n * per * 2, w1 + n * per, dscale + n * per, q + n * 4);
+    return FDGS_OK;
 }

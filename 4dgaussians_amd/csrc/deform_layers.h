@@ -33,24 +33,7 @@ constexpr int GCOLS = 64;
 __host__ __device__ __forceinline__ int head_row0(int hd) { return hd == 0 ? 0 : hd == 1 ? 3 : hd == 2 ? 6 : hd == 3 ? 10 : 11; }
 
 // ------------------------------------------------------------------------------------------------ HexPlane gather
-struct AxisSample {
-    int i0, i1;
-    float w0, w1, dscale;  // dscale = d pixel / d coord, 0 where the border clamp is active
-};
-// grid_sample(align_corners=True, padding_mode='border') un-normalisation (scene/hexplane.py:39-43)
-__device__ __forceinline__ AxisSample axis_sample(float coord, int size) {
-    AxisSample s;
-    const float hi = (float)(size - 1);
-    float p = ((coord + 1.f) * 0.5f) * hi;
-    s.dscale = (p > 0.f && p < hi) ? 0.5f * hi : 0.f;
-    p = fminf(fmaxf(p, 0.f), hi);
-    const float f = floorf(p);
-    s.i0 = (int)f;
-    s.i1 = s.i0 + 1 < size ? s.i0 + 1 : size - 1;
-    s.w1 = p - f;
-    s.w0 = 1.f - s.w1;
-    return s;
-}
+// AxisSample, axis_sample and query_coord -- the index arithmetic -- live in hexplane_ops.h (contraction off, shared with the host twin)
 __device__ __forceinline__ void plane_axes(int k, int& a, int& b) {
     // pairs (0,1),(0,2),(0,3),(1,2),(1,3),(2,3): a indexes the plane's width, b its height
     a = k < 3 ? 0 : (k < 5 ? 1 : 2);
@@ -121,7 +104,7 @@ __device__ __forceinline__ float4 gather_chunk(const fdgs_deform_params& p, int 
 __device__ __forceinline__ void load_query(const fdgs_deform_params& p, const AabbScale& sc, int n, float* q, float* xyz) {
     xyz[0] = p.xyz[3 * (size_t)n]; xyz[1] = p.xyz[3 * (size_t)n + 1]; xyz[2] = p.xyz[3 * (size_t)n + 2];
 #pragma unroll
-    for (int i = 0; i < 3; i++) q[i] = (xyz[i] - p.aabb[i]) * sc.inv2[i] - 1.0f;
+    for (int i = 0; i < 3; i++) q[i] = query_coord(xyz[i], p.aabb[i], sc.inv2[i]);
     q[3] = p.time ? p.time[n] : p.time_scalar;
 }
 

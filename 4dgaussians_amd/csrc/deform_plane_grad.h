@@ -51,7 +51,7 @@ __global__ void __launch_bounds__(PG_THREADS) deform_plane_grad_kernel(PlaneGrad
         const int n = n_raw < n_end ? n_raw : n_end - 1;
         float q[4];
 #pragma unroll
-        for (int i = 0; i < 3; i++) q[i] = (xn[i] - p.aabb[i]) * a.sc.inv2[i] - 1.0f;
+        for (int i = 0; i < 3; i++) q[i] = query_coord(xn[i], p.aabb[i], a.sc.inv2[i]);
         q[3] = xn[3];
         if (nb + GPB < n_end) fetch_xyz(nb + GPB, xn);
         float dq[3] = {0.f, 0.f, 0.f};
@@ -282,7 +282,7 @@ __global__ void __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) deform_plane_grad_
             const bool live = by_rows ? !(ent & ROW_PAD) : (n < p.N && a.tile_live[nn >> 5] != 0u);   // (rows of dead tiles do not stretch the window)
 #pragma unroll
             for (int i = 0; i < 3; i++) {
-                const float q = (p.xyz[3 * (size_t)nn + i] - p.aabb[i]) * a.sc.inv2[i] - 1.0f;
+                const float q = query_coord(p.xyz[3 * (size_t)nn + i], p.aabb[i], a.sc.inv2[i]);
                 s_q[i * G + tid] = q;
                 s_dq[tid * 3 + i] = 0.f;
                 float m = live ? q : 3.0e38f;

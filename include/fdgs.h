@@ -305,6 +305,20 @@ int fdgs_deform_bwd(void* stream, const fdgs_deform_params* p, const fdgs_deform
  * out_host[2] = plane-gradient chunks processed, out_host[3] = chunks in total.  Synchronises the stream. */
 int fdgs_deform_bwd_live_tiles(void* stream, const fdgs_deform_params* p, const void* scratch, uint32_t* out_host);
 
+/* HexPlane index arithmetic (additions to ABI 6; no existing signature changed): a probe of the texel cells every deformation kernel takes,
+ * and its host twin.  The arithmetic is one host/device function per operation (csrc/hexplane_ops.h, contraction off): q = ((x - aabb[i]) *
+ * (2 / (aabb[3+i] - aabb[i]))) - 1, three roundings like the reference's normalize_aabb; pixel = ((q + 1) * 0.5) * (size - 1), border clamp,
+ * floor.  The *_host twin returns, over host arrays and without a GPU, bit for bit what the device entry point writes, and both equal
+ * F.grid_sample(align_corners=True, padding_mode='border') on float32 (tests/golden/hexplane_cells.npz).
+ *   p       only N, xyz, time / time_scalar, aabb, L and res are read; planes (and everything else) may be NULL / zero
+ *   cells   int32 [N][L][4][2]: (i0, i1) of axes x, y, z, t per level, i1 = min(i0 + 1, size - 1)
+ *   w1      float [N][L][4]: weight of i1 (the weight of i0 is 1 - w1)
+ *   dscale  float [N][L][4]: d pixel / d coordinate = (size - 1) / 2, 0 where the border clamp is active
+ *   q       float [N][4]: the normalised coordinates (q[3] = the time, which is never normalised)
+ * The probe is ONE launch on `stream` of a one-thread-per-Gaussian kernel; it is never part of a frame. */
+int fdgs_hexplane_cells(void* stream, const fdgs_deform_params* p, int32_t* cells, float* w1, float* dscale, float* q);
+int fdgs_hexplane_cells_host(const fdgs_deform_params* p, int32_t* cells, float* w1, float* dscale, float* q);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Loss-side helper for the frame-parallel driver: accumulates [sum|a-b|, sum (a-b)^2, n] into acc[3] (device,
  * caller zero-fills) and optionally writes dL/da = sign(a-b)*scale.  (utils/loss_utils.py:20-21, image_utils.py:17-38)

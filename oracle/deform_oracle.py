@@ -139,15 +139,18 @@ def deform_forward(sd, flags, xyz, scales, rotations, opacity, shs, t, activate=
     return pts, sc, rot, op, sh
 
 
-def discontinuity_margin(sd, flags, xyz, t):
+def discontinuity_margin(sd, flags, xyz, t, parts=False):
     """Per Gaussian: distance to the nearest derivative discontinuity of the deformation field = min over
     (|pre-activation| of every ReLU input, distance of every spatial plane coordinate to a texel boundary in pixels).
-    Tests use it to pick inputs on which float rounding cannot flip a ReLU or a bilinear cell."""
+    Tests use it to pick inputs on which float rounding cannot flip a ReLU or a bilinear cell.
+    parts=True returns (relu part, cell part) instead of their minimum: the kernels' texel cells equal this oracle's exactly
+    (csrc/hexplane_ops.h), so only the ReLU part can excuse a row whose gradient differs."""
     with torch.no_grad():
         n_levels = count_levels(sd)
         feat = hexplane_features(sd, xyz, t, n_levels)
         hidden = F.linear(feat, sd["deformation_net.feature_out.0.weight"], sd["deformation_net.feature_out.0.bias"])
         margin = hidden.abs().min(dim=1).values
+        cell = torch.full_like(margin, float("inf"))
         for (name, flag, k) in HEADS:
             if getattr(flags, flag):
                 continue
@@ -163,8 +166,8 @@ def discontinuity_margin(sd, flags, xyz, t):
                 frac = (p - torch.floor(p)).clamp(0, 1)
                 dist = torch.minimum(frac, 1 - frac)
                 dist = torch.where((p < 0) | (p > size - 1), torch.minimum((p - 0).abs(), (p - (size - 1)).abs()), dist)
-                margin = torch.minimum(margin, dist * 0.1)
-    return margin
+                cell = torch.minimum(cell, dist * 0.1)
+    return (margin, cell) if parts else torch.minimum(margin, cell)
 
 
 def backward_float64(sd, flags, leaves, t_value, gouts):

@@ -72,6 +72,7 @@ typedef struct {
     /* per-Gaussian state */
     REAL *depth, *xy, *conic_opacity, *rgb, *cov3D;
     int *radii, *tiles_touched;
+    REAL *radius_pre; /* 3*sqrt(max(l1,l2)) before the ceil (0 where the Gaussian was culled earlier): how close a radius sits to its ceil boundary */
     uint8_t *clamped;
     uint32_t *rect; /* xmin ymin xmax ymax */
     /* binning */
@@ -200,7 +201,7 @@ void oracle_raster_free(void *h) {
     Oracle *o = (Oracle *)h;
     if (!o) return;
     free(o->depth); free(o->xy); free(o->conic_opacity); free(o->rgb); free(o->cov3D);
-    free(o->radii); free(o->tiles_touched); free(o->clamped); free(o->rect);
+    free(o->radii); free(o->radius_pre); free(o->tiles_touched); free(o->clamped); free(o->rect);
     free(o->pair_tile); free(o->pair_gid); free(o->ranges); free(o->final_T); free(o->n_contrib);
     free(o);
 }
@@ -227,6 +228,7 @@ void *oracle_raster_forward(int P, int D, int M, const REAL *bg, int W, int H, c
     o->depth = xcalloc(P, sizeof(REAL)); o->xy = xcalloc(2 * (size_t)P, sizeof(REAL));
     o->conic_opacity = xcalloc(4 * (size_t)P, sizeof(REAL)); o->rgb = xcalloc(3 * (size_t)P, sizeof(REAL));
     o->cov3D = xcalloc(6 * (size_t)P, sizeof(REAL)); o->radii = xcalloc(P, sizeof(int));
+    o->radius_pre = xcalloc(P, sizeof(REAL));
     o->tiles_touched = xcalloc(P, sizeof(int)); o->clamped = xcalloc(3 * (size_t)P, 1);
     o->rect = xcalloc(4 * (size_t)P, sizeof(uint32_t));
 
@@ -260,7 +262,8 @@ void *oracle_raster_forward(int P, int D, int M, const REAL *bg, int W, int H, c
         REAL mid = (REAL)0.5 * (a + c);
         REAL sq = R_SQRT(R_FMAX(LAMBDA_FLOOR, mid * mid - det));
         REAL l1 = mid + sq, l2 = mid - sq;
-        REAL my_radius = R_CEIL(RADIUS_SIGMA * R_SQRT(R_FMAX(l1, l2)));
+        o->radius_pre[i] = RADIUS_SIGMA * R_SQRT(R_FMAX(l1, l2));
+        REAL my_radius = R_CEIL(o->radius_pre[i]);
         REAL px = ndc2pix(pp[0], W), py = ndc2pix(pp[1], H);
         int rx0 = (int)((px - my_radius) / (REAL)TILE), ry0 = (int)((py - my_radius) / (REAL)TILE);
         int rx1 = (int)((px + my_radius + (REAL)(TILE - 1)) / (REAL)TILE), ry1 = (int)((py + my_radius + (REAL)(TILE - 1)) / (REAL)TILE);
@@ -383,7 +386,7 @@ const void *oracle_raster_field(void *h, int which) {
         case 0: return o->depth; case 1: return o->xy; case 2: return o->conic_opacity; case 3: return o->rgb;
         case 4: return o->cov3D; case 5: return o->radii; case 6: return o->tiles_touched; case 7: return o->clamped;
         case 8: return o->pair_tile; case 9: return o->pair_gid; case 10: return o->ranges; case 11: return o->final_T;
-        case 12: return o->n_contrib; case 13: return o->rect;
+        case 12: return o->n_contrib; case 13: return o->rect; case 14: return o->radius_pre;
     }
     return 0;
 }

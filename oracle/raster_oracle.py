@@ -19,6 +19,7 @@ FIELDS = {
     "depth": (0, "real", 1), "xy": (1, "real", 2), "conic_opacity": (2, "real", 4), "rgb": (3, "real", 3),
     "cov3D": (4, "real", 6), "radii": (5, np.int32, 1), "tiles_touched": (6, np.int32, 1),
     "clamped": (7, np.uint8, 3), "rect": (13, np.uint32, 4),
+    "radius_pre": (14, "real", 1),     # 3*sqrt(max(l1,l2)) before the ceil
 }
 
 

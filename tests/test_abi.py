@@ -28,6 +28,7 @@ def test_every_declared_symbol_is_exported_and_bound(L):
     lib = L.lib()
     names = _header_symbols()
     assert len(names) >= 18
+    assert {"fdgs_hexplane_cells", "fdgs_hexplane_cells_host"} <= set(names)      # the probe of the HexPlane index arithmetic and its host twin
     for n in names:
         assert hasattr(lib, n), n
         assert n in L.SYMBOLS, f"{n} declared in fdgs.h but not bound in _lib.SYMBOLS"

@@ -57,6 +57,27 @@ def test_float32_build_close_to_float64():
         assert rel_l2(g32[k], g64[k]) < 1e-3, k
 
 
+def _raster_cases():
+    import test_gpu_raster
+    return test_gpu_raster.CASES
+
+
+@pytest.mark.parametrize("i", range(6))
+def test_radius_pre_field_and_its_float32_error(i):
+    """The oracle's pre-ceil radius 3*sqrt(max(l1,l2)): its ceil is the radius, and over the scenes of tests/test_gpu_raster.py the float32 build
+    differs from the float64 build by at most RADII_PRE_F32_VS_F64 relative -- the measurement behind that test's ceil-boundary margin."""
+    import test_gpu_raster
+    sc = raster_scene(**_raster_cases()[i])
+    o32, o64 = RasterOracle(**sc), RasterOracle(**sc, dtype=np.float64)
+    a, b = o32.field("radius_pre"), o64.field("radius_pre")
+    vis = o32.radii > 0
+    assert np.array_equal(np.ceil(a[vis]).astype(np.int32), o32.radii[vis]) and np.array_equal(np.ceil(b[o64.radii > 0]).astype(np.int32), o64.radii[o64.radii > 0])
+    m = (a > 0) & (b > 0)
+    rel = float((np.abs(a[m].astype(np.float64) - b[m]) / b[m]).max())
+    print(f"case {i}: largest relative f32-vs-f64 difference of the pre-ceil radius {rel:.3g}")
+    assert rel <= test_gpu_raster.RADII_PRE_F32_VS_F64
+
+
 def _single(px_offset=0.0, opacity=0.8, s=0.05, W=65, H=65, z=4.0, bg=(0.0, 0.0, 0.0)):
     # camera at origin looking down +z: identity view; projection with tanfov=0.5
     tanf = 0.5
