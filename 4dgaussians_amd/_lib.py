@@ -251,3 +251,8 @@ def stream_ptr():
 def ptr(t):
     """Device pointer of a torch tensor (None -> NULL)."""
     return None if t is None else c_void_p(t.data_ptr())
+
+
+def f32(t):
+    """The tensor as contiguous float32 (itself where it already is), None for None: what the C ABI reads."""
+    return None if t is None else t.float().contiguous()

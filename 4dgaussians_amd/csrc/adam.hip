@@ -74,7 +74,7 @@ extern "C" int fdgs_adam_step(void* stream_, int ntensors, const fdgs_adam_tenso
             if (s.n == 0) continue;
             FDGS_REQUIRE(s.param && s.grad && s.exp_avg && s.exp_avg_sq, "adam: NULL tensor pointer");
             FDGS_REQUIRE(s.step >= 1, "adam: step counts from 1");
-            FDGS_REQUIRE((((uintptr_t)s.param | (uintptr_t)s.grad | (uintptr_t)s.exp_avg | (uintptr_t)s.exp_avg_sq) & 15) == 0,
+            FDGS_REQUIRE(aligned_to(s.param, 16) && aligned_to(s.grad, 16) && aligned_to(s.exp_avg, 16) && aligned_to(s.exp_avg_sq, 16),
                          "adam: tensors must be 16-byte aligned");
             FDGS_REQUIRE(s.n < (1ull << 32), "adam: tensor too large");
             AdamT& T = a.t[cnt++];

@@ -217,7 +217,7 @@ extern "C" int fdgs_l1_stats(void* stream_, size_t n, const float* a, const floa
     FDGS_REQUIRE(a && b && acc, "NULL pointer");
     if (n == 0) return FDGS_OK;
     hipStream_t stream = (hipStream_t)stream_;
-    const bool aligned = (((uintptr_t)a | (uintptr_t)b | (uintptr_t)grad_out_opt) & 15) == 0;
+    const bool aligned = aligned_to(a, 16) && aligned_to(b, 16) && aligned_to(grad_out_opt, 16);
     const size_t n4 = aligned ? n / 4 : 0;
     int blocks = (int)(((aligned ? n / 4 : n) + L1S_THREADS - 1) / L1S_THREADS);
     if (blocks < 1) blocks = 1;
@@ -237,7 +237,7 @@ extern "C" int fdgs_l1_stats_assign(void* stream_, size_t n, const float* a, con
                                     float* acc, void* scratch) {
     FDGS_REQUIRE(a && b && acc && scratch, "NULL pointer");
     hipStream_t stream = (hipStream_t)stream_;
-    const bool aligned = (((uintptr_t)a | (uintptr_t)b | (uintptr_t)grad_out_opt) & 15) == 0;
+    const bool aligned = aligned_to(a, 16) && aligned_to(b, 16) && aligned_to(grad_out_opt, 16);
     const size_t n4 = aligned ? n / 4 : 0;
     int blocks = (int)(((aligned ? n / 4 : n) + L1S_THREADS - 1) / L1S_THREADS);
     if (blocks < 1) blocks = 1;

@@ -12,6 +12,7 @@
 // digit counters in LDS, keys regrouped by digit in LDS so that the global scatter writes contiguous runs.  A sort over
 // nbits key bits runs ceil(nbits / 8) passes of near-equal digit width (32 -> 8,8,8,8; the 13-bit tile id -> 7,6).
 #include "common.h"
+#include "raster.h"
 
 namespace fdgs {
 
@@ -221,10 +222,8 @@ __global__ void __launch_bounds__(SORT_THREADS) radix_scatter_kernel(const uint3
     }
 }
 
-// LSD radix sort of n (key,val) pairs over bits [0,nbits). Ping-pongs between (k0,v0) and (k1,v1); returns which
-// buffer holds the result (0 or 1) through *result_in.
 int radix_sort_pairs(hipStream_t stream, uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t n, int nbits,
-                     uint32_t* hist, int nblocks, int debug, int* result_in, int items = SORT_ITEMS, const uint32_t* n_dev = nullptr) {
+                     uint32_t* hist, int nblocks, int debug, int* result_in, int items, const uint32_t* n_dev) {
     int cur = 0;
     if (n > 0) {
         const int npass = (nbits + RADIX_BITS - 1) / RADIX_BITS;
@@ -397,13 +396,9 @@ __global__ void __launch_bounds__(256) tile_ranges_kernel(const uint32_t* __rest
     }
 }
 
-int validate_raster_params(const fdgs_raster_params* p);
-
 }  // namespace fdgs
 
 using namespace fdgs;
-
-int fdgs_preprocess_fwd_impl(void* stream_, const fdgs_raster_params* p, void* geom, int32_t* radii, uint32_t* host_count_dev);   // preprocess.hip
 
 extern "C" int fdgs_geom_bytes(int P, size_t* bytes) {
     FDGS_REQUIRE(P >= 0 && bytes, "bad arguments");
@@ -461,10 +456,7 @@ static int bin_prepare_impl(void* stream_, const fdgs_raster_params* p, void* ge
         hipLaunchKernelGGL((scan_chunk_kernel<true>), dim3(nchunks), dim3(256), 0, stream, at<uint32_t>(geom, gl.tiles),
                            at<uint32_t>(geom, gl.ids0), at<uint32_t>(geom, gl.offsets), (uint32_t)p->P, bsum);
     }
-    {
-        hipError_t e_ = hipGetLastError();
-        if (e_ != hipSuccess) { return fail(FDGS_E_HIP, "kernel %s failed: %s", "scan_tiles", hipGetErrorString(e_)); }
-    }
+    FDGS_LAUNCH_CHECK("scan_tiles", 0, stream);
     if (wait) {
         hipError_t e = hipEventSynchronize(ev);
         if (e != hipSuccess) return fail(FDGS_E_HIP, "%s failed: %s", "hipEventSynchronize", hipGetErrorString(e));

@@ -87,6 +87,7 @@ inline int device_cus() {
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }     // (NULL is aligned to everything)
 
 // block-wide exclusive prefix of one value per thread (256 threads); *total = sum over the block
 __device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t* wtmp /*[4] LDS*/, uint32_t* total) {

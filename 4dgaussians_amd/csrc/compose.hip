@@ -128,7 +128,6 @@ __global__ void __launch_bounds__(256) state_place_kernel(const PlaceArgs g) {
     }
 }
 
-static inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 static int check_place(const fdgs_placement* p, int N, unsigned field_mask, const fdgs_state_arrays* a, const fdgs_state_arrays* b, float w,
                        const fdgs_state_arrays* out, bool device) {

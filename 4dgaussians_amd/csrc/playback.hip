@@ -245,7 +245,6 @@ __global__ void __launch_bounds__(256) state_extent_kernel(const ExtentArgs g) {
     g.extent[5 * n + sub] = e;
 }
 
-static inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 static inline const float* field_of(const fdgs_state_arrays* s, int h) {
     return h == 0 ? s->xyz : h == 1 ? s->scales : h == 2 ? s->rotations : h == 3 ? s->opacity : s->shs;

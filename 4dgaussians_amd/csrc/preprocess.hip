@@ -5,6 +5,7 @@
 // Replaces preprocessCUDA / computeCov2DCUDA of the un-vendored rasterizer.
 #include "common.h"
 #include "gs_math.h"
+#include "raster.h"
 
 namespace fdgs {
 
@@ -22,10 +23,20 @@ __device__ __forceinline__ void load_cam(CamConst& c, const float* __restrict__ 
     c.D = D; c.M = M;
 }
 
-struct PreFwdArgs {
+// what both projection kernels take first: the frame's camera and the inputs the forward and the backward both read
+struct FrameHead {
     int P, D, M, W, H;
     float tanfovx, tanfovy, scale_mod;
-    const float *view, *proj, *campos, *means3D, *shs, *colors_precomp, *opacities, *scales, *rotations, *cov3D_precomp;
+    const float *view, *proj, *campos, *means3D, *shs;
+};
+static void fill_frame_head(FrameHead& a, const fdgs_raster_params* p) {
+    a.P = p->P; a.D = p->sh_degree; a.M = p->sh_coeffs; a.W = p->W; a.H = p->H;
+    a.tanfovx = p->tanfovx; a.tanfovy = p->tanfovy; a.scale_mod = p->scale_modifier;
+    a.view = p->viewmatrix; a.proj = p->projmatrix; a.campos = p->campos; a.means3D = p->means3D; a.shs = p->shs;
+}
+
+struct PreFwdArgs : FrameHead {
+    const float *colors_precomp, *opacities, *scales, *rotations, *cov3D_precomp;
     float* depth; float4 *recA, *recB, *recC; float* cov3D;
     uint32_t *tiles, *clamped; uint2* rect; uint32_t *keys, *ids, *total, *host_count;
     int32_t* radii;
@@ -149,10 +160,8 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreFwdArgs a) {
     if (i == 0) a.total[2] = a.cull ? 1u : 0u;   // the pair expansion reads which list semantics the counts have
 }
 
-struct PreBwdArgs {
-    int P, D, M, W, H;
-    float tanfovx, tanfovy, scale_mod;
-    const float *view, *proj, *campos, *means3D, *shs, *scales, *rotations;
+struct PreBwdArgs : FrameHead {
+    const float *scales, *rotations;
     int has_cov_precomp;
     const float* cov3D; const uint32_t *tiles, *clamped;
     const float* gacc;           // [P,16] packed sums written by render_bwd (layout in render.hip)
@@ -479,7 +488,6 @@ int validate_raster_params(const fdgs_raster_params* p) {
 
 using namespace fdgs;
 
-// host_count_dev (capacity mode): device address of the pinned host word that receives the pair count from the kernel's last workgroup
 int fdgs_preprocess_fwd_impl(void* stream_, const fdgs_raster_params* p, void* geom, int32_t* radii, uint32_t* host_count_dev) {
     int rc = validate_raster_params(p);
     if (rc) return rc;
@@ -489,9 +497,7 @@ int fdgs_preprocess_fwd_impl(void* stream_, const fdgs_raster_params* p, void* g
     FDGS_HIP_CHECK(hipMemsetAsync(at<char>(geom, gl.total), 0, 256, stream));
     if (p->P == 0) return FDGS_OK;
     PreFwdArgs a{};
-    a.P = p->P; a.D = p->sh_degree; a.M = p->sh_coeffs; a.W = p->W; a.H = p->H;
-    a.tanfovx = p->tanfovx; a.tanfovy = p->tanfovy; a.scale_mod = p->scale_modifier;
-    a.view = p->viewmatrix; a.proj = p->projmatrix; a.campos = p->campos; a.means3D = p->means3D; a.shs = p->shs;
+    fill_frame_head(a, p);
     a.colors_precomp = p->colors_precomp; a.opacities = p->opacities; a.scales = p->scales; a.rotations = p->rotations;
     a.cov3D_precomp = p->cov3D_precomp;
     a.depth = at<float>(geom, gl.depth); a.recA = at<float4>(geom, gl.recA); a.recB = at<float4>(geom, gl.recB);
@@ -515,28 +521,27 @@ int fdgs_launch_preprocess_bwd(hipStream_t stream, const fdgs_raster_params* p, 
     if (p->P == 0) return FDGS_OK;
     GeomLayout gl = geom_layout(p->P);
     PreBwdArgs a{};
-    a.P = p->P; a.D = p->sh_degree; a.M = p->sh_coeffs; a.W = p->W; a.H = p->H;
-    a.tanfovx = p->tanfovx; a.tanfovy = p->tanfovy; a.scale_mod = p->scale_modifier;
-    a.view = p->viewmatrix; a.proj = p->projmatrix; a.campos = p->campos; a.means3D = p->means3D; a.shs = p->shs;
+    fill_frame_head(a, p);
     a.scales = p->scales; a.rotations = p->rotations; a.has_cov_precomp = p->cov3D_precomp != nullptr;
     a.cov3D = at<float>(geom, gl.cov3D); a.tiles = at<uint32_t>(geom, gl.tiles); a.clamped = at<uint32_t>(geom, gl.clamped);
     a.dL_dmeans2D = g->dL_dmeans2D; a.gacc = g->scratch_acc; a.dL_dopacity = g->dL_dopacity;
     a.dL_dcolors = g->dL_dcolors; a.dL_dmeans3D = g->dL_dmeans3D; a.dL_dsh = g->dL_dsh; a.dL_dscales = g->dL_dscales;
     a.dL_drot = g->dL_drotations; a.dL_dcov3D = g->dL_dcov3D;
     a.opacities = p->opacities;
-    if (g->deform_epilogue) {
-        const fdgs_raster_deform_epilogue* e = g->deform_epilogue;
+    const fdgs_raster_deform_epilogue* e = g->deform_epilogue;
+    if (e) {
         FDGS_REQUIRE(p->shs && p->sh_coeffs == 16 && p->scales && p->rotations && !p->cov3D_precomp,
                      "deform_epilogue needs SH (16 coefficients) and scale/rotation inputs");
         FDGS_REQUIRE(e->G && e->Npad >= p->P && e->Npad % 128 == 0 && (!e->activate || e->rot_norm), "bad deform_epilogue");
-        FDGS_REQUIRE(!e->zero_fill || ((reinterpret_cast<uintptr_t>(e->zero_fill) & 15) == 0 && (e->zero_floats & 3) == 0),
+        FDGS_REQUIRE(!e->zero_fill || (aligned_to(e->zero_fill, 16) && (e->zero_floats & 3) == 0),
                      "deform_epilogue.zero_fill must be 16-byte aligned with a multiple of 4 floats");
         a.epi = *e;
-        { FDGS_TIMED("preprocess_bwd", stream); hipLaunchKernelGGL(preprocess_bwd_kernel<true>, dim3(cdiv(e->Npad, 256)), dim3(256), 0, stream, a); }
-        FDGS_LAUNCH_CHECK("preprocess_bwd", p->debug, stream);
-        return FDGS_OK;
     }
-    { FDGS_TIMED("preprocess_bwd", stream); hipLaunchKernelGGL(preprocess_bwd_kernel<false>, dim3(cdiv(p->P, 256)), dim3(256), 0, stream, a); }
+    {
+        FDGS_TIMED("preprocess_bwd", stream);
+        if (e) hipLaunchKernelGGL(preprocess_bwd_kernel<true>, dim3(cdiv(e->Npad, 256)), dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL(preprocess_bwd_kernel<false>, dim3(cdiv(p->P, 256)), dim3(256), 0, stream, a);
+    }
     FDGS_LAUNCH_CHECK("preprocess_bwd", p->debug, stream);
     return FDGS_OK;
 }

@@ -91,7 +91,7 @@ extern "C" int fdgs_plane_regulation(void* stream_, int nplanes, const fdgs_reg_
         const fdgs_reg_plane& s = planes[i];
         FDGS_REQUIRE(s.plane && s.H >= 1 && s.W >= 1 && s.C >= 4 && s.C % 4 == 0, "plane must be channels-last [H][W][C], C % 4 == 0");
         FDGS_REQUIRE((long long)s.H * s.W * s.C < (1ll << 31), "plane too large");
-        FDGS_REQUIRE((((uintptr_t)s.plane | (uintptr_t)s.grad_opt) & 15) == 0, "plane pointers must be 16-byte aligned");
+        FDGS_REQUIRE(aligned_to(s.plane, 16) && aligned_to(s.grad_opt, 16), "plane pointers must be 16-byte aligned");
         RegPlane& P = a.pl[i];
         P.p = s.plane; P.g = s.grad_opt; P.H = s.H; P.RS4 = s.W * s.C / 4;
         // mean over [C, H-2, W]; torch's mean of an empty tensor is NaN (H < 3): same here

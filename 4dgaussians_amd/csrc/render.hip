@@ -13,6 +13,7 @@
 // Replaces renderCUDA forward/backward of the un-vendored rasterizer (Appendix B.3/B.4).
 #include "common.h"
 #include "gs_math.h"
+#include "raster.h"
 
 namespace fdgs {
 
@@ -113,18 +114,22 @@ __device__ __forceinline__ float blend_power(float u1, float cx, float cyy, floa
     const float q = u1 + u2;
     return __builtin_fmaf(q, -0.5f, -c2);
 }
-typedef float v2f_ __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ v2f_ blend_power2(float u1, float cx, float cyy, v2f_ dy) {
+typedef float v2f __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ v2f blend_power2(float u1, float cx, float cyy, v2f dy) {
 #pragma clang fp contract(off)
-    const v2f_ u2 = dy * (dy * cyy);
-    const v2f_ c2 = dy * cx;
-    const v2f_ q = u1 + u2;
-    return __builtin_elementwise_fma(q, v2f_{-0.5f, -0.5f}, -c2);
+    const v2f u2 = dy * (dy * cyy);
+    const v2f c2 = dy * cx;
+    const v2f q = u1 + u2;
+    return __builtin_elementwise_fma(q, v2f{-0.5f, -0.5f}, -c2);
 }
 
-struct RenderArgs {
+// what both blending kernels take first: the image's tile grid and the block -> tile map
+struct BlendHead {
     int W, H, gx, gy, bh;
     const uint32_t* order; int per_xcd;      // heaviest-first tile order (nullptr: image order)
+};
+
+struct RenderArgs : BlendHead {
     uint32_t* tile_todo;                     // out, per tile: max n_contrib = the entries the backward will walk
     const uint2* ranges; const uint32_t* pair_gid;
     const float4 *recA, *recB, *recC;
@@ -268,9 +273,7 @@ __device__ __forceinline__ float wave_reduce_scatter10(float a0, float a1, float
     return __uint_as_float(q[0]) + __uint_as_float(q[1]);                      // lower half: e01 totals, upper half: e2 totals
 }
 
-struct RenderBwdArgs {
-    int W, H, gx, gy, bh;
-    const uint32_t* order; int per_xcd;      // heaviest-first tile order (nullptr: image order)
+struct RenderBwdArgs : BlendHead {
     const uint2* ranges; const uint32_t* pair_gid;
     const float4 *recA, *recB, *recC;
     const float* bg;
@@ -438,7 +441,6 @@ __global__ void __launch_bounds__(256) render_bwd_kernel(RenderBwdArgs a) {
 //     entry later);
 //   * a wave is its own workgroup: it stages its own 64 entries per round (records prefetched one round ahead, list ids two), never
 //     waits for another wave, and sends its sums straight to the gradient line (lanes 0..NV-1, one atomic instruction per entry).
-typedef float v2f __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ v2f splat2(float x) { return v2f{x, x}; }
 
@@ -581,10 +583,6 @@ __global__ void __launch_bounds__(64) render_bwd_strip_kernel(RenderBwdArgs a) {
     }
 }
 
-int validate_raster_params(const fdgs_raster_params* p);
-
-// tile rows per XCD group (unit_of_block): common.h XCD_ROWS (0 was one contiguous band per XCD)
-static int tile_rows_per_xcd_group(int) { return XCD_ROWS; }
 // launches tile_order_kernel when the knob is on and an XCD's tiles fit its LDS sort; returns the order to hand to the kernel (or nullptr)
 static const uint32_t* make_tile_order(hipStream_t stream, int mode, const ImgLayout& il, const void* img, void* img_w) {
     if (!g_tune.tile_order || il.per_xcd > TILE_ORDER_MAX || il.per_xcd < 1) return nullptr;
@@ -595,9 +593,33 @@ static const uint32_t* make_tile_order(hipStream_t stream, int mode, const ImgLa
     return order;
 }
 
-}  // namespace fdgs
+// what both blending launchers set from the frame's buffers (Args = RenderArgs with a writable img, RenderBwdArgs with a const one);
+// `order` stays with the launcher: making it is a launch
+template <typename Args, typename Img>
+static ImgLayout fill_blend_args(Args& a, const fdgs_raster_params* p, const void* geom, const void* binning, Img* img, uint32_t R) {
+    const GeomLayout gl = geom_layout(p->P);
+    const BinLayout bl = bin_layout(R);
+    const ImgLayout il = img_layout(p->W, p->H);
+    a.W = p->W; a.H = p->H; a.gx = il.gx; a.gy = il.gy; a.bh = XCD_ROWS; a.per_xcd = il.per_xcd;
+    a.ranges = at<uint2>(img, il.ranges); a.pair_gid = binning ? at<uint32_t>(binning, bl.gid0) : nullptr;
+    a.recA = at<float4>(geom, gl.recA); a.recB = at<float4>(geom, gl.recB); a.recC = at<float4>(geom, gl.recC);
+    a.bg = p->bg; a.final_T = at<float>(img, il.final_T); a.n_contrib = at<uint32_t>(img, il.n_contrib);
+    return il;
+}
 
-int fdgs_launch_preprocess_bwd(hipStream_t stream, const fdgs_raster_params* p, const void* geom, const fdgs_raster_grads* g);
+// The blending backward's form.  ppl = pixels per lane of the strip form (one wave per workgroup, 4 / ppl of them per tile); anything but
+// 2 or 4 = the 256-thread form (128 entries staged per round keeps six workgroups per CU at 25 KB of LDS each).  depth: dL_ddepth was
+// handed in.  (The tables name the instantiations in the order the device code has always listed them.)
+static void launch_render_bwd(hipStream_t stream, int ppl, bool depth, const RenderBwdArgs& a) {
+    using Kernel = void (*)(RenderBwdArgs);
+    static const Kernel strip[2][2] = {{render_bwd_strip_kernel<true, 1>, render_bwd_strip_kernel<true, 2>},
+                                       {render_bwd_strip_kernel<false, 1>, render_bwd_strip_kernel<false, 2>}};
+    static const Kernel whole[2] = {render_bwd_kernel<true, 128>, render_bwd_kernel<false, 128>};
+    if (ppl == 2 || ppl == 4) hipLaunchKernelGGL(strip[depth ? 0 : 1][ppl / 4], dim3(unit_grid(a.gx, a.gy, 4 / ppl, a.bh)), dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL(whole[depth ? 0 : 1], dim3(unit_grid(a.gx, a.gy, 1, a.bh)), dim3(256), 0, stream, a);
+}
+
+}  // namespace fdgs
 
 using namespace fdgs;
 
@@ -607,16 +629,10 @@ extern "C" int fdgs_render_fwd(void* stream_, const fdgs_raster_params* p, const
     if (rc) return rc;
     FDGS_REQUIRE(geom && img && out_color && out_depth && (binning || R == 0), "NULL buffer");
     hipStream_t stream = (hipStream_t)stream_;
-    GeomLayout gl = geom_layout(p->P);
-    BinLayout bl = bin_layout(R);
-    ImgLayout il = img_layout(p->W, p->H);
     RenderArgs a{};
-    a.W = p->W; a.H = p->H; a.gx = il.gx; a.gy = il.gy; a.bh = tile_rows_per_xcd_group(il.gy);
-    a.ranges = at<uint2>(img, il.ranges); a.pair_gid = binning ? at<uint32_t>(binning, bl.gid0) : nullptr;
-    a.recA = at<float4>(geom, gl.recA); a.recB = at<float4>(geom, gl.recB); a.recC = at<float4>(geom, gl.recC);
-    a.bg = p->bg; a.final_T = at<float>(img, il.final_T); a.n_contrib = at<uint32_t>(img, il.n_contrib);
+    const ImgLayout il = fill_blend_args(a, p, geom, binning, img, R);
     a.out_color = out_color; a.out_depth = out_depth;
-    a.tile_todo = at<uint32_t>(img, il.todo); a.per_xcd = il.per_xcd;
+    a.tile_todo = at<uint32_t>(img, il.todo);
     a.zfill = reinterpret_cast<float4*>(p->acc_zero); a.zfill_n4 = (uint32_t)p->P * 4u;
     a.order = R > 0 ? make_tile_order(stream, 0, il, img, img) : nullptr;
     {
@@ -649,42 +665,20 @@ extern "C" int fdgs_raster_bwd(void* stream_, const fdgs_raster_params* p, const
         if (g->dL_dscales) FDGS_HIP_CHECK(hipMemsetAsync(g->dL_dscales, 0, P * 12, stream));
         if (g->dL_drotations) FDGS_HIP_CHECK(hipMemsetAsync(g->dL_drotations, 0, P * 16, stream));
     }
-    GeomLayout gl = geom_layout(p->P);
-    BinLayout bl = bin_layout(R);
-    ImgLayout il = img_layout(p->W, p->H);
     if (R > 0) {
         RenderBwdArgs a{};
-        a.W = p->W; a.H = p->H; a.gx = il.gx; a.gy = il.gy; a.bh = tile_rows_per_xcd_group(il.gy);
-        a.ranges = at<uint2>(img, il.ranges); a.pair_gid = at<uint32_t>(binning, bl.gid0);
-        a.recA = at<float4>(geom, gl.recA); a.recB = at<float4>(geom, gl.recB); a.recC = at<float4>(geom, gl.recC);
-        a.bg = p->bg; a.final_T = at<float>(img, il.final_T); a.n_contrib = at<uint32_t>(img, il.n_contrib);
+        const ImgLayout il = fill_blend_args(a, p, geom, binning, img, R);
         a.dL_dcolor = g->dL_dcolor; a.dL_ddepth = g->dL_ddepth;
         a.gacc = g->scratch_acc;
         // (the order lists live in `img`, the forward's state, which this call otherwise only reads: the slice written here is scratch of the
         // backward that belongs to this frame -- one backward per forward state at a time, as for every other buffer of the state)
-        a.per_xcd = il.per_xcd;
         a.order = make_tile_order(stream, 1, il, img, const_cast<void*>(img));
         {
             FDGS_TIMED("render_bwd", stream);
-            // (256-thread form: 128 entries staged per round keeps six workgroups per CU at 25 KB of LDS each)
-            const dim3 grid(unit_grid(a.gx, a.gy, 1, a.bh));
-            // pixels per lane of the strip form (1 wave per workgroup); 0 = the 256-thread form
             // -1 (default): by image size -- one wave per tile leaves the chip underfilled when the image has fewer tiles than the chip has wave
             // slots (1 024 SIMDs x 4): two waves per tile then (config 3, 2 040 tiles: blending backward 0.274 -> 0.213 ms; config 2, 2 500
             // tiles: 0.197 -> 0.187; at 5 440 tiles four pixels per lane win by 10 %, profiles/r05_rbwd_ppl_small_images_ab.txt)
-            const int ppl = g_tune.rbwd_ppl >= 0 ? g_tune.rbwd_ppl : (a.gx * a.gy <= 4096 ? 2 : 4);
-            if (ppl == 2 || ppl == 4) {
-                const dim3 sgrid(unit_grid(a.gx, a.gy, 4 / ppl, a.bh));
-#define FDGS_STRIP(D_, P_) hipLaunchKernelGGL((render_bwd_strip_kernel<D_, P_>), sgrid, dim3(64), 0, stream, a)
-                if (g->dL_ddepth) { if (ppl == 2) FDGS_STRIP(true, 1); else FDGS_STRIP(true, 2); }
-                else if (ppl == 2) FDGS_STRIP(false, 1);
-                else FDGS_STRIP(false, 2);
-#undef FDGS_STRIP
-            } else if (g->dL_ddepth) {
-                hipLaunchKernelGGL((render_bwd_kernel<true, 128>), grid, dim3(256), 0, stream, a);
-            } else {
-                hipLaunchKernelGGL((render_bwd_kernel<false, 128>), grid, dim3(256), 0, stream, a);
-            }
+            launch_render_bwd(stream, g_tune.rbwd_ppl >= 0 ? g_tune.rbwd_ppl : (a.gx * a.gy <= 4096 ? 2 : 4), g->dL_ddepth != nullptr, a);
         }
         FDGS_LAUNCH_CHECK("render_bwd", p->debug, stream);
     }

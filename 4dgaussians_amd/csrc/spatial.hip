@@ -8,12 +8,10 @@
 // Launches per fdgs_spatial_order: [bbox partials + bbox final when bounds are NULL] + keys + 3 x ceil(3 * bits / 8) radix launches (30 bits:
 // digit widths 8, 8, 7, 7), all on the caller's stream, no synchronisation, no read-back.
 #include "common.h"
+#include "raster.h"
 #include "spatial_keys.h"
 
 namespace fdgs {
-
-int radix_sort_pairs(hipStream_t stream, uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t n, int nbits,
-                     uint32_t* hist, int nblocks, int debug, int* result_in, int items, const uint32_t* n_dev);   // binning.hip
 
 constexpr int BBOX_MAX_BLOCKS = 256;                 // partial boxes (one per workgroup of the first reduction launch)
 constexpr int BBOX_POINTS_PER_BLOCK = 256 * 16;

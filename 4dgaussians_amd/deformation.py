@@ -615,10 +615,9 @@ def note_live_tiles(st, b):
         last_live_tiles = tuple(int(x) for x in out)
 
 
-def backward_run(st, b):
-    """Launches fdgs_deform_bwd on prepared buffers and returns the gradients in _DeformFunction's input order (after cfg, t_scalar)."""
-    check(_lib.lib().fdgs_deform_bwd(stream_ptr(), st.p, b.g))
-    note_live_tiles(st, b)
+def gradient_tuple(st, b):
+    """The arena's views in _DeformFunction's input order (after cfg, t_scalar): (d_xyz, d_sc, d_rot, d_op, d_sha, d_shb, None [time],
+    None [aabb], planes..., mlp...), in the inputs' shapes.  The fused render Functions slice it."""
     cfg, sh = st.cfg, st.shapes
     d_mlp = b.d_mlp
     for h in range(NUM_HEADS):  # parameters of a disabled head receive no gradient (as under autograd)
@@ -627,6 +626,13 @@ def backward_run(st, b):
     return (b.d_xyz, b.d_sc.reshape(sh["scales"]), b.d_rot.reshape(sh["rot"]), b.d_op.reshape(sh["op"]),
             b.d_sha.reshape(sh["sh_a"]), None if b.d_shb is None else b.d_shb.reshape(sh["sh_b"]), None, None,
             *b.d_planes, *d_mlp)
+
+
+def backward_run(st, b):
+    """Launches fdgs_deform_bwd on prepared buffers and returns the gradients (gradient_tuple)."""
+    check(_lib.lib().fdgs_deform_bwd(stream_ptr(), st.p, b.g))
+    note_live_tiles(st, b)
+    return gradient_tuple(st, b)
 
 
 class _DeformFunction(torch.autograd.Function):
@@ -649,8 +655,7 @@ class _DeformFunction(torch.autograd.Function):
         st = ctx.st
         o_sc, o_rot, o_op = ctx.saved_tensors
         b = backward_prepare(st, o_sc, o_rot, o_op)
-        c = lambda t: None if t is None else t.float().contiguous()
-        gx, gs, gr, go, gsh = c(g_xyz), c(g_sc), c(g_rot), c(g_op), c(g_sh)
+        gx, gs, gr, go, gsh = map(_lib.f32, (g_xyz, g_sc, g_rot, g_op, g_sh))
         g = b.g
         g.g_xyz, g.g_scales, g.g_rotations, g.g_opacity, g.g_shs = ptr(gx), ptr(gs), ptr(gr), ptr(go), ptr(gsh)
         return (None, None) + backward_run(st, b)

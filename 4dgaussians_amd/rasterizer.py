@@ -72,7 +72,7 @@ _SENTINEL = 0xFFFFFFFF
 _RING = 64
 _tls = threading.local()
 _seen = {}            # (device index, W, H, P) -> [largest pair count seen, P it was seen at]
-_size_cache = {}      # ("geom", P) / ("img", W, H) / ("bin", R) -> bytes
+_size_cache = {}      # ("geom", P) / ("img", W, H) / ("binning", R, W, H) -> bytes
 
 
 class PairCount:
@@ -133,12 +133,7 @@ def _bytes(L, kind, *args):
     v = _size_cache.get(key)
     if v is None:
         nbytes = _lib.c_size_t()
-        if kind == "geom":
-            check(L.fdgs_geom_bytes(args[0], nbytes))
-        elif kind == "img":
-            check(L.fdgs_img_bytes(args[0], args[1], nbytes))
-        else:
-            check(L.fdgs_binning_bytes(args[0], args[1], args[2], nbytes))
+        check(getattr(L, f"fdgs_{kind}_bytes")(*args, nbytes))
         if len(_size_cache) > 256:
             _size_cache.clear()
         v = _size_cache[key] = nbytes.value
@@ -156,9 +151,7 @@ def _f32(t, device):
         return None
     if t.device != device:
         t = t.to(device)
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
+    return (t if t.dtype == torch.float32 else t.float()).contiguous()
 
 
 def _none_if_empty(t):
@@ -183,71 +176,89 @@ class RasterState:
         return int(self.count.value())
 
 
-def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, out=None, expect_backward=False):
-    """Runs stages 1-4 of include/fdgs.h. Returns (color, radii, depth, state).  `out` = (color [3,H,W], radii [P] int32, depth [1,H,W])
-    buffers to write into (contiguous float32 / int32 on the device), e.g. slices of a batch tensor.  `expect_backward`: a training frame
-    (the blending forward zero-fills the backward's accumulator on the way).  Which binning path runs: BINNING above -- every mode but the
-    opt-in "capacity" returns the exact path's image."""
-    L = _lib.lib()
+def _frame_params(settings, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp):
+    """(fdgs_raster_params of one frame, the eleven tensors it points at).  The tensors are normalised first: float32 and contiguous on the
+    device of means3D, empty optional inputs -> None; visibility and acc_zero are rasterize_forward's to allocate."""
     dev = means3D.device
-    if not _is_hip_device(dev):
-        raise _lib.FdgsError("the rasterizer runs on the GPU only (tensors must live on a HIP device)")
     means3D = _f32(means3D, dev)
-    P = means3D.shape[0]
-    H, W = int(settings.image_height), int(settings.image_width)
     shs, colors_precomp = _f32(_none_if_empty(shs), dev), _f32(_none_if_empty(colors_precomp), dev)
     scales, rotations = _f32(_none_if_empty(scales), dev), _f32(_none_if_empty(rotations), dev)
     cov3D_precomp, opacities = _f32(_none_if_empty(cov3D_precomp), dev), _f32(opacities, dev)
     bg, view = _f32(settings.bg, dev), _f32(settings.viewmatrix, dev)
     proj, campos = _f32(settings.projmatrix, dev), _f32(settings.campos, dev)
-    if (shs is None) == (colors_precomp is None) and P > 0:
-        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-    if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-            ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-        if P > 0:
+    if means3D.shape[0] > 0:         # (an empty set may come without either)
+        if (shs is None) == (colors_precomp is None):
+            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+    P = means3D.shape[0]
     p = RasterParams()
-    p.P, p.sh_degree, p.W, p.H = P, int(settings.sh_degree), W, H
+    p.P, p.sh_degree, p.W, p.H = P, int(settings.sh_degree), int(settings.image_width), int(settings.image_height)
     p.sh_coeffs = 0 if shs is None else int(shs.numel() // max(P, 1) // 3)
     p.tanfovx, p.tanfovy, p.scale_modifier = float(settings.tanfovx), float(settings.tanfovy), float(settings.scale_modifier)
     p.prefiltered, p.debug = int(bool(settings.prefiltered)), int(bool(settings.debug))
     p.bg, p.viewmatrix, p.projmatrix, p.campos = ptr(bg), ptr(view), ptr(proj), ptr(campos)
     p.means3D, p.shs, p.colors_precomp, p.opacities = ptr(means3D), ptr(shs), ptr(colors_precomp), ptr(opacities)
     p.scales, p.rotations, p.cov3D_precomp = ptr(scales), ptr(rotations), ptr(cov3D_precomp)
-    geom = torch.empty(_bytes(L, "geom", P), dtype=torch.uint8, device=dev)
-    img = torch.empty(_bytes(L, "img", W, H), dtype=torch.uint8, device=dev)
-    if out is not None:
-        color, radii, depth = out
-    else:
-        radii = torch.empty(P, dtype=torch.int32, device=dev)
-        color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
-        depth = torch.empty(1, H, W, dtype=torch.float32, device=dev)
-    vis = torch.empty(P, dtype=torch.bool, device=dev)       # radii > 0, written by the projection kernel (no elementwise launch)
-    p.visibility = ptr(vis)
-    # a training frame: the blending forward zero-fills the backward's per-Gaussian accumulator on the way (no fill launch before the backward)
-    acc = torch.empty(P, 16, device=dev) if expect_backward and P > 0 else None
-    p.acc_zero = ptr(acc)
-    st = stream_ptr()
+    return p, (means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, bg, view, proj, campos)
+
+
+def _claim_count(dev, key, P):
+    """(the PairCount of a new forward: the next word of this thread's ring of pinned words, what the predictor has seen for `key`, the
+    counts still in flight).  Counts of earlier frames that have arrived meanwhile feed the predictor on the way (never waits)."""
     tstate, ring = _thread_state(dev)
     pending = tstate["pending"]
-    if pending:           # counts of earlier frames that have arrived meanwhile: feed the predictor (never waits)
+    if pending:
         tstate["pending"] = pending = [c for c in pending if c.poll() is None]
-    key = (dev.index, W, H, P)          # (another model / a densified set: another key, i.e. one exact frame first)
     seen = _seen.get(key)
     cnt = PairCount()
-    cnt.key, cnt.P, cnt.R, cnt.stream = key, P, None, None
+    cnt.key, cnt.P, cnt.R, cnt.stream, cnt.capacity = key, P, None, None, None
     cnt.buf = ring[0]                    # (keeps the pinned ring alive for as long as anything may read or write this word)
     slot = ring[1] = (ring[1] + 1) % _RING
     cnt.addr = ring[0].data_ptr() + 4 * slot
     for c in pending:          # (a count still in flight in this slot -- 64 forwards old: cannot happen on a live device -- is waited for, never overwritten)
         if c.addr == cnt.addr:
             c.value()
+    return cnt, seen, pending
+
+
+def _finish_exact(L, st, p, geom, img, cnt, color, depth):
+    """Stages 3-4 on a binning buffer of the true size, cnt.R pairs (stages 1-2 are complete in `geom`) -> (binning, cnt.R)."""
+    binning = torch.empty(_bytes(L, "binning", cnt.R, p.W, p.H), dtype=torch.uint8, device=geom.device)
+    check(L.fdgs_bin_sort(st, p, ptr(geom), ptr(binning), ptr(img), cnt.R))
+    check(L.fdgs_render_fwd(st, p, ptr(geom), ptr(binning), ptr(img), cnt.R, ptr(color), ptr(depth)))
+    return binning, cnt.R
+
+
+def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, out=None, expect_backward=False):
+    """Runs stages 1-4 of include/fdgs.h. Returns (color, radii, depth, state).  `out` = (color [3,H,W], radii [P] int32, depth [1,H,W])
+    buffers to write into (contiguous float32 / int32 on the device), e.g. slices of a batch tensor.  `expect_backward`: a training frame
+    (the blending forward zero-fills the backward's accumulator on the way).  Which binning path runs: BINNING above -- every mode but the
+    opt-in "capacity" returns the exact path's image."""
+    global capacity_reruns
+    L = _lib.lib()
+    dev = means3D.device
+    if not _is_hip_device(dev):
+        raise _lib.FdgsError("the rasterizer runs on the GPU only (tensors must live on a HIP device)")
+    p, tensors = _frame_params(settings, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp)
+    P, W, H = p.P, p.W, p.H
+    geom = torch.empty(_bytes(L, "geom", P), dtype=torch.uint8, device=dev)
+    img = torch.empty(_bytes(L, "img", W, H), dtype=torch.uint8, device=dev)
+    color, radii, depth = out if out is not None else (torch.empty(3, H, W, dtype=torch.float32, device=dev),
+                                                       torch.empty(P, dtype=torch.int32, device=dev), torch.empty(1, H, W, dtype=torch.float32, device=dev))
+    vis = torch.empty(P, dtype=torch.bool, device=dev)       # radii > 0, written by the projection kernel (no elementwise launch)
+    p.visibility = ptr(vis)
+    # a training frame: the blending forward zero-fills the backward's per-Gaussian accumulator on the way (no fill launch before the backward)
+    acc = torch.empty(P, 16, device=dev) if expect_backward and P > 0 else None
+    p.acc_zero = ptr(acc)
+    st = stream_ptr()
+    cnt, seen, pending = _claim_count(dev, (dev.index, W, H, P), P)      # (another model / a densified set: another key, i.e. one exact frame first)
     speculative = BINNING == "auto" or (BINNING == "capacity" and len(pending) < _RING - 2)
     if speculative and seen is not None and P > 0:
-        global capacity_reruns
         cap = (int(seen[0] * CAPACITY_SLACK) + 8192) // 4096 * 4096
         ctypes.c_uint32.from_address(cnt.addr).value = _SENTINEL
-        binning = torch.empty(_bytes(L, "bin", cap, W, H), dtype=torch.uint8, device=dev)
+        binning = torch.empty(_bytes(L, "binning", cap, W, H), dtype=torch.uint8, device=dev)
         check(L.fdgs_raster_fwd_capacity(st, p, ptr(geom), ptr(binning), ptr(img), cap, _lib.c_void_p(cnt.addr), ptr(radii), ptr(color), ptr(depth)))
         if BINNING == "capacity":      # opt-in: never waits; the count is looked at when a later frame starts
             cnt.capacity = cap
@@ -256,32 +267,34 @@ def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales,
         else:                          # verified: the image this call returns is the exact path's
             true_n = _lib.c_uint32()
             check(L.fdgs_pair_count_wait(st, _lib.c_void_p(cnt.addr), true_n))
-            cnt.capacity = None
             cnt.R = true_n.value
             _note_count(cnt)
-            if cnt.R > cap:            # the speculative frame dropped pairs: finish it exactly (stages 1-2 are complete in `geom`)
+            if cnt.R > cap:            # the speculative frame dropped pairs: finish it exactly
                 capacity_reruns += 1
-                cap = cnt.R
-                binning = torch.empty(_bytes(L, "bin", cap, W, H), dtype=torch.uint8, device=dev)
-                check(L.fdgs_bin_sort(st, p, ptr(geom), ptr(binning), ptr(img), cap))
-                check(L.fdgs_render_fwd(st, p, ptr(geom), ptr(binning), ptr(img), cap, ptr(color), ptr(depth)))
+                binning, cap = _finish_exact(L, st, p, geom, img, cnt, color, depth)
     else:
         check(L.fdgs_preprocess_fwd(st, p, ptr(geom), ptr(radii)))
         check(L.fdgs_bin_prepare(st, p, ptr(geom), _lib.c_void_p(cnt.addr)))          # (blocks until the count is in host memory)
-        cap = ctypes.c_uint32.from_address(cnt.addr).value
-        cnt.capacity = None
-        cnt.R = cap
+        cnt.R = ctypes.c_uint32.from_address(cnt.addr).value
         _note_count(cnt)
-        binning = torch.empty(_bytes(L, "bin", cap, W, H), dtype=torch.uint8, device=dev)
-        check(L.fdgs_bin_sort(st, p, ptr(geom), ptr(binning), ptr(img), cap))
-        check(L.fdgs_render_fwd(st, p, ptr(geom), ptr(binning), ptr(img), cap, ptr(color), ptr(depth)))
-    tstate["last"] = cnt
+        binning, cap = _finish_exact(L, st, p, geom, img, cnt, color, depth)
+    _tls.st["last"] = cnt
     state = RasterState()
     state.params, state.geom, state.binning, state.img, state.capacity, state.count = p, geom, binning, img, cap, cnt
-    state.visibility = vis
-    state.acc = acc
-    state.keep = (means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, bg, view, proj, campos)
+    state.visibility, state.acc, state.keep = vis, acc, tensors
     return color, radii, depth, state
+
+
+def fill_raster_grads(state, grad_color, grad_depth, d_means2D, epilogue=None):
+    """The fdgs_raster_grads every backward of `state` starts from: the image gradients, where the screen-space gradient goes, the
+    accumulator (state.take_accumulator: the one the forward zero-filled, once) and -- fused backward -- the deformation epilogue the
+    per-Gaussian chain rule writes through instead of the other outputs.  Returns (g, accumulator); the caller keeps what g points at."""
+    g = RasterGrads()
+    acc, g.scratch_acc_zeroed = state.take_accumulator()
+    g.dL_dcolor, g.dL_ddepth, g.dL_dmeans2D, g.scratch_acc = ptr(grad_color), ptr(grad_depth), ptr(d_means2D), ptr(acc)
+    if epilogue is not None:
+        g.deform_epilogue = ctypes.pointer(epilogue)
+    return g, acc
 
 
 def rasterize_backward(state, grad_color, grad_depth=None):
@@ -290,20 +303,16 @@ def rasterize_backward(state, grad_color, grad_depth=None):
     p = state.params
     means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp = state.keep[:7]
     dev, P = means3D.device, p.P
-    g = RasterGrads()
-    grad_color = _f32(grad_color, dev)
-    grad_depth = _f32(grad_depth, dev)
+    grad_color, grad_depth = _f32(grad_color, dev), _f32(grad_depth, dev)
     out = dict(means2D=torch.empty(P, 3, device=dev), means3D=torch.empty(P, 3, device=dev),
                opacities=torch.empty(P, 1, device=dev), colors=torch.empty(P, 3, device=dev),
                cov3D=torch.empty(P, 6, device=dev),
                shs=None if shs is None else torch.empty(P, p.sh_coeffs, 3, device=dev),
                scales=None if scales is None else torch.empty(P, 3, device=dev),
                rotations=None if rotations is None else torch.empty(P, 4, device=dev))
-    scratch, g.scratch_acc_zeroed = state.take_accumulator()
-    g.dL_dcolor, g.dL_ddepth = ptr(grad_color), ptr(grad_depth)
-    g.dL_dmeans2D, g.dL_dmeans3D, g.dL_dopacity = ptr(out["means2D"]), ptr(out["means3D"]), ptr(out["opacities"])
-    g.dL_dcolors, g.dL_dsh, g.dL_dscales = ptr(out["colors"]), ptr(out["shs"]), ptr(out["scales"])
-    g.dL_drotations, g.dL_dcov3D, g.scratch_acc = ptr(out["rotations"]), ptr(out["cov3D"]), ptr(scratch)
+    g, scratch = fill_raster_grads(state, grad_color, grad_depth, out["means2D"])
+    g.dL_dmeans3D, g.dL_dopacity, g.dL_dcolors, g.dL_dcov3D = ptr(out["means3D"]), ptr(out["opacities"]), ptr(out["colors"]), ptr(out["cov3D"])
+    g.dL_dsh, g.dL_dscales, g.dL_drotations = ptr(out["shs"]), ptr(out["scales"]), ptr(out["rotations"])
     check(L.fdgs_raster_bwd(stream_ptr(), p, ptr(state.geom), ptr(state.binning), ptr(state.img), state.capacity, g))
     return out
 

@@ -95,6 +95,35 @@ def _fill_epilogue(st, b, assign):
     return epi
 
 
+def _fused_backward(states, saved, grad_colors, grad_depths, **prepare):
+    """The backward of the fused fine stage for the views of one autograd node: states = [(deformation state, raster state)], saved = their
+    (o_sc, o_rot, o_op) in a row, grad_colors / grad_depths = the per-view image gradients (or None), `prepare` goes to backward_prepare.
+    Last view first (its saved activations, lists and records are the ones still partly resident in the 256 MB Infinity Cache), per view: the
+    rasterizer backward, whose epilogue writes into the ONE gradient arena (the first processed view assigns the identity paths, later ones
+    accumulate), then that view's deformation backward -- same output pointers and scratch (stream-ordered reuse), its own saved activations."""
+    L, stream = _lib.lib(), _lib.stream_ptr()
+    st0 = states[0][0]
+    b = _deformation.backward_prepare(st0, saved[0], saved[1], saved[2], identity_assigned=EPILOGUE_ASSIGN, **prepare)
+    dev = b.d_xyz.device
+    g_means2D, keep = [None] * len(states), []
+    for k_, v in enumerate(reversed(range(len(states)))):
+        st, rstate = states[v]
+        p = rstate.params
+        gc = _lib.f32(grad_colors[v]) if grad_colors is not None else torch.zeros(3, p.H, p.W, device=dev)
+        gd = _lib.f32(grad_depths[v]) if grad_depths is not None else None
+        gm = g_means2D[v] = torch.empty(p.P, 3, device=dev)
+        epi = _fill_epilogue(st, b, EPILOGUE_ASSIGN and k_ == 0)
+        g, acc = _rasterizer.fill_raster_grads(rstate, gc, gd, gm, epi)      # (acc: zero-filled by the blending forward of this frame, no fill launch here)
+        _lib.check(L.fdgs_raster_bwd(stream, p, _lib.ptr(rstate.geom), _lib.ptr(rstate.binning), _lib.ptr(rstate.img), rstate.capacity, g))
+        b.g.out_scales, b.g.out_rotations, b.g.out_opacity = _lib.ptr(saved[3 * v]), _lib.ptr(saved[3 * v + 1]), _lib.ptr(saved[3 * v + 2])
+        b.g.rot_norm, b.g.saved = _lib.ptr(st.o_norm), _lib.ptr(st.saved_act)
+        b.g.packed_rows_ready = epi.tile_flags + 1
+        _lib.check(L.fdgs_deform_bwd(stream, st.p, b.g))
+        _deformation.note_live_tiles(st, b)
+        keep.append((gc, gd, acc, epi))      # (what the queued launches read lives until the last of them is queued)
+    return g_means2D, _deformation.gradient_tuple(st0, b)      # ([d means2D per view], the arena's views in _DeformFunction's input order)
+
+
 class _FusedRenderFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg, t_scalar, raster_settings, means2D, xyz, scales, rotations, opacity, sh_a, sh_b, aabb, *rest):
@@ -112,30 +141,13 @@ class _FusedRenderFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_vis=None):
-        st, rstate = ctx.st, ctx.rstate
-        n_in = 11 + len(st.plane_shapes) + len(st.keep[0][8])
+        st = ctx.st
         if grad_color is None and grad_depth is None:
-            return (None,) * n_in
-        L = _lib.lib()
-        o_sc, o_rot, o_op = ctx.saved_tensors
-        b = _deformation.backward_prepare(st, o_sc, o_rot, o_op, identity_assigned=EPILOGUE_ASSIGN, zero_by_epilogue=EPILOGUE_ASSIGN)
-        p = rstate.params
-        dev, P = b.d_xyz.device, p.P
-        if grad_color is None:
-            grad_color = torch.zeros(3, p.H, p.W, device=dev)
-        f = lambda t: None if t is None else t.float().contiguous()
-        grad_color, grad_depth = f(grad_color), f(grad_depth)
-        g = _lib.RasterGrads()
-        g_means2D = torch.empty(P, 3, device=dev)
-        acc, g.scratch_acc_zeroed = rstate.take_accumulator()       # (zero-filled by the blending forward of this frame: no fill launch here)
-        g.dL_dcolor, g.dL_ddepth, g.dL_dmeans2D, g.scratch_acc = _lib.ptr(grad_color), _lib.ptr(grad_depth), _lib.ptr(g_means2D), _lib.ptr(acc)
-        epi = _fill_epilogue(st, b, EPILOGUE_ASSIGN)
-        g.deform_epilogue = _lib.ctypes.pointer(epi)
-        _lib.check(L.fdgs_raster_bwd(_lib.stream_ptr(), p, _lib.ptr(rstate.geom), _lib.ptr(rstate.binning), _lib.ptr(rstate.img),
-                                     rstate.capacity, g))
-        b.g.packed_rows_ready = epi.tile_flags + 1
-        grads = _deformation.backward_run(st, b)       # (d_xyz, d_sc, d_rot, d_op, d_sha, d_shb, None [time], None [aabb], planes..., mlp...)
-        return (None, None, None, g_means2D) + grads[:6] + grads[7:]
+            return (None,) * (11 + len(st.plane_shapes) + len(st.keep[0][8]))
+        # one view; the epilogue kernel also clears the accumulate-into part of the arena on the way
+        g_means2D, grads = _fused_backward([(st, ctx.rstate)], ctx.saved_tensors, None if grad_color is None else (grad_color,),
+                                           None if grad_depth is None else (grad_depth,), zero_by_epilogue=EPILOGUE_ASSIGN)
+        return (None, None, None, *g_means2D) + grads[:6] + grads[7:]       # (grads[6]: the time tensor, no input here)
 
 
 class _FusedRenderViewsFunction(torch.autograd.Function):
@@ -172,48 +184,11 @@ class _FusedRenderViewsFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_colors, grad_radii, grad_depths):
-        states, nviews = ctx.states, ctx.nviews
-        st0 = states[0][0]
-        n_in = 4 + nviews + 7 + len(st0.plane_shapes) + len(st0.keep[0][8])
+        st0 = ctx.states[0][0]
         if grad_colors is None and grad_depths is None:
-            return (None,) * n_in
-        L = _lib.lib()
-        saved = ctx.saved_tensors
-        b = _deformation.backward_prepare(st0, saved[0], saved[1], saved[2], identity_assigned=EPILOGUE_ASSIGN)
-        dev = b.d_xyz.device
-        f = lambda t: None if t is None else t.float().contiguous()
-        g_means2D = [None] * nviews
-        keep = []
-        # last view first: its saved activations, lists and records are the ones still (partly) resident in the 256 MB Infinity Cache
-        for k_, v in enumerate(reversed(range(nviews))):
-            st, rstate = states[v]
-            p = rstate.params
-            P = p.P
-            gc = f(grad_colors[v]) if grad_colors is not None else torch.zeros(3, p.H, p.W, device=dev)
-            gd = f(grad_depths[v]) if grad_depths is not None else None
-            g = _lib.RasterGrads()
-            gm = torch.empty(P, 3, device=dev)
-            acc, g.scratch_acc_zeroed = rstate.take_accumulator()
-            g.dL_dcolor, g.dL_ddepth, g.dL_dmeans2D, g.scratch_acc = _lib.ptr(gc), _lib.ptr(gd), _lib.ptr(gm), _lib.ptr(acc)
-            epi = _fill_epilogue(st, b, EPILOGUE_ASSIGN and k_ == 0)      # later views accumulate into what the first processed one assigned
-            g.deform_epilogue = _lib.ctypes.pointer(epi)
-            _lib.check(L.fdgs_raster_bwd(_lib.stream_ptr(), p, _lib.ptr(rstate.geom), _lib.ptr(rstate.binning), _lib.ptr(rstate.img),
-                                         rstate.capacity, g))
-            # this view's deformation backward: same output pointers and scratch (stream-ordered reuse), its own saved activations
-            b.g.out_scales, b.g.out_rotations, b.g.out_opacity = _lib.ptr(saved[3 * v]), _lib.ptr(saved[3 * v + 1]), _lib.ptr(saved[3 * v + 2])
-            b.g.rot_norm, b.g.saved = _lib.ptr(st.o_norm), _lib.ptr(st.saved_act)
-            b.g.packed_rows_ready = epi.tile_flags + 1
-            _lib.check(L.fdgs_deform_bwd(_lib.stream_ptr(), st.p, b.g))
-            _deformation.note_live_tiles(st, b)
-            g_means2D[v] = gm
-            keep.append((gc, gd, acc, epi))
-        cfg, sh = st0.cfg, st0.shapes
-        d_mlp = b.d_mlp
-        for h in range(_lib.NUM_HEADS):
-            if not cfg["head_on"][h]:
-                d_mlp[2 + 4 * h:6 + 4 * h] = [None] * 4
-        return (None, None, None, None, *g_means2D, b.d_xyz, b.d_sc.reshape(sh["scales"]), b.d_rot.reshape(sh["rot"]), b.d_op.reshape(sh["op"]),
-                b.d_sha.reshape(sh["sh_a"]), None if b.d_shb is None else b.d_shb.reshape(sh["sh_b"]), None, *b.d_planes, *d_mlp)
+            return (None,) * (4 + ctx.nviews + 7 + len(st0.plane_shapes) + len(st0.keep[0][8]))
+        g_means2D, grads = _fused_backward(ctx.states, ctx.saved_tensors, grad_colors, grad_depths)
+        return (None, None, None, None, *g_means2D) + grads[:6] + grads[7:]
 
 
 def render_views(viewpoint_cameras, pc, pipe, bg_color, scaling_modifier=1.0, stage="fine", cam_type=None):

@@ -17,6 +17,8 @@ class _FakeLib:
         self.calls = []
         self.record = False         # True: keep the non-pointer struct fields of the calls below (the front-end tests)
         self.deform, self.raster, self.epilogue = [], [], []
+        self.pair_count = 7         # what the "device" counts for the next forward
+        self.pairs, self.grads, self.bwd_views = [], [], []
 
     def __getattr__(self, name):
         if not name.startswith("fdgs_"):
@@ -29,9 +31,9 @@ class _FakeLib:
             if name in ("fdgs_geom_bytes", "fdgs_img_bytes", "fdgs_binning_bytes", "fdgs_deform_saved_bytes", "fdgs_deform_bwd_scratch_bytes"):
                 a[-1].value = 4096
             elif name == "fdgs_bin_prepare":
-                ctypes.cast(a[3], ctypes.POINTER(ctypes.c_uint32))[0] = 7
+                ctypes.cast(a[3], ctypes.POINTER(ctypes.c_uint32))[0] = self.pair_count
             elif name == "fdgs_raster_fwd_capacity":      # (the device would deliver the count later; the fake delivers it at once)
-                ctypes.cast(a[6], ctypes.POINTER(ctypes.c_uint32))[0] = 7
+                ctypes.cast(a[6], ctypes.POINTER(ctypes.c_uint32))[0] = self.pair_count
             elif name == "fdgs_pair_count_wait":
                 a[2].value = ctypes.cast(a[1], ctypes.POINTER(ctypes.c_uint32))[0]
             elif name == "fdgs_deform_bwd_live_tiles":
@@ -57,9 +59,18 @@ class _FakeLib:
             p = a[1]
             self.raster.append({k: getattr(p, k) for k in ("P", "sh_degree", "sh_coeffs", "W", "H", "tanfovx", "tanfovy", "scale_modifier",
                                                            "prefiltered", "debug")})
-        elif name == "fdgs_raster_bwd" and a[6].deform_epilogue:
-            e = a[6].deform_epilogue.contents
-            self.epilogue.append((e.assign, e.tile_flags, e.activate, e.Npad, e.zero_floats))
+            if name == "fdgs_raster_fwd_capacity":
+                self.pairs.append(("raster_fwd_capacity", int(a[5])))       # (the capacity its binning buffer is laid out for)
+        elif name in ("fdgs_bin_sort", "fdgs_render_fwd"):
+            self.pairs.append((name[len("fdgs_"):], int(a[5])))       # (the pair count the binning buffer is laid out for)
+        elif name == "fdgs_deform_bwd":       # whose activated outputs / rotation norms this deformation backward reads
+            self.bwd_views.append((a[2].out_scales, a[2].out_rotations, a[2].out_opacity, a[2].rot_norm))
+        elif name == "fdgs_raster_bwd":
+            g = a[6]
+            self.grads.append(" ".join(k for k, _ in g._fields_ if getattr(g, k)))      # the non-NULL pointers (and scratch_acc_zeroed = 1)
+            if g.deform_epilogue:
+                e = g.deform_epilogue.contents
+                self.epilogue.append((e.assign, e.tile_flags, e.activate, e.Npad, e.zero_floats))
 
 
 @pytest.fixture
@@ -436,3 +447,60 @@ def test_fused_backwards_fill_the_epilogue_as_before(fake):
     fake.epilogue.clear()
     _run_render_views(fake, 300)
     assert fake.epilogue == PARENT_EPILOGUE_VIEWS and [e[0] for e in fake.epilogue] == [1, 0, 0]
+
+
+# ---- the rasterizer's host side: recorded at the commit BEFORE its stage arguments and the fused backward body came to be written once -------
+PARENT_RERUN_CALLS = f"{_CAP} binning_bytes bin_sort render_fwd"
+PARENT_RERUN_PAIRS = [("raster_fwd_capacity", 8192), ("bin_sort", 9426), ("render_fwd", 9426)]
+PARENT_RERUN_STATE = (1, 0, 9426, 9426, 9426)        # capacity_reruns gained, capacity_overflows, state.capacity, .num_rendered, last_num_rendered()
+PARENT_AFTER_RERUN = (_CAP, 20480, 9426, 1)          # the next frame: calls, state.capacity, .num_rendered, capacity_reruns gained so far
+_FUSED_GRADS = "dL_dcolor dL_dmeans2D scratch_acc deform_epilogue scratch_acc_zeroed"
+PARENT_GRADS_TWO_NODE = ["dL_dcolor dL_dmeans2D dL_dmeans3D dL_dopacity dL_dcolors dL_dsh dL_dscales dL_drotations dL_dcov3D scratch_acc scratch_acc_zeroed"]
+PARENT_GRADS_FUSED = [_FUSED_GRADS]
+PARENT_GRADS_VIEWS = [_FUSED_GRADS, _FUSED_GRADS, _FUSED_GRADS]
+
+
+def test_a_speculative_frame_that_overflows_its_capacity_is_finished_exactly(fake):
+    """BINNING = "auto": the second frame of a (size, count) key is queued for a predicted capacity; when its count proves larger, stages 3-4
+    run again on a buffer of the true size before rasterize_forward returns, and the state describes THAT buffer."""
+    R = fdgs.rasterizer
+    assert R.BINNING == "auto"
+    fake.record = True
+    pc = _model(300)
+    cam = _cam(0.5)
+    settings = R.GaussianRasterizationSettings(48, 64, 0.36, 0.27, torch.zeros(3), 1.0, cam.world_view_transform, cam.full_proj_transform, 3,
+                                               cam.camera_center, False, False)
+    args = (settings, pc.get_xyz.detach(), torch.rand(300, 16, 3), None, torch.rand(300, 1), torch.rand(300, 3), torch.rand(300, 4), None)
+    *_, first = R.rasterize_forward(*args)
+    assert first.capacity == first.num_rendered == 7
+    cap = (int(7 * R.CAPACITY_SLACK) + 8192) // 4096 * 4096
+    fake.pair_count = cap + 1234
+    fake.calls.clear()
+    fake.pairs.clear()
+    reruns = R.capacity_reruns
+    *_, state = R.rasterize_forward(*args)
+    assert " ".join(c[len("fdgs_"):] for c in fake.calls) == PARENT_RERUN_CALLS
+    assert fake.pairs == PARENT_RERUN_PAIRS and fake.pairs[0][1] == cap and state.capacity == cap + 1234     # (the state's capacity is the true count)
+    assert (R.capacity_reruns - reruns, R.capacity_overflows, state.capacity, state.num_rendered, R.last_num_rendered()) == PARENT_RERUN_STATE
+    fake.calls.clear()                        # the predictor has learnt: the next frame fits
+    *_, third = R.rasterize_forward(*args)
+    assert (" ".join(c[len("fdgs_"):] for c in fake.calls), third.capacity, third.num_rendered, R.capacity_reruns - reruns) == PARENT_AFTER_RERUN
+
+
+def test_raster_backwards_hand_over_the_gradient_buffers_they_handed_over_before(fake, monkeypatch):
+    """Which fdgs_raster_grads pointers are non-NULL (and scratch_acc_zeroed): the two-node backward asks for every per-Gaussian gradient, the
+    fused ones only for the screen-space means -- the rest goes through the deformation epilogue."""
+    fake.record = True
+    monkeypatch.setattr(fdgs.renderer, "FUSED_BACKWARD", False)
+    _run_render_backward(fake, 300)
+    assert fake.grads == PARENT_GRADS_TWO_NODE
+    monkeypatch.setattr(fdgs.renderer, "FUSED_BACKWARD", True)
+    fake.grads.clear()
+    _run_render_backward(fake, 300)
+    assert fake.grads == PARENT_GRADS_FUSED
+    fake.grads.clear()
+    fake.bwd_views.clear()
+    _run_render_views(fake, 300)
+    assert fake.grads == PARENT_GRADS_VIEWS
+    # every view's deformation backward reads that view's own forward outputs (three views: twelve distinct buffers)
+    assert len(fake.bwd_views) == 3 and len({q for view in fake.bwd_views for q in view}) == 12 and None not in fake.bwd_views[0]
