@@ -168,6 +168,10 @@ SYMBOLS = {
                                  POINTER(StateArrays)]),
     "fdgs_state_place_host": (c_int, [POINTER(Placement), c_int, c_uint32, POINTER(StateArrays), POINTER(StateArrays), c_float,
                                       POINTER(StateArrays)]),
+    "fdgs_state_place_rows": (c_int, [c_void_p, POINTER(Placement), c_int, c_void_p, c_int, c_uint32, POINTER(StateArrays),
+                                      POINTER(StateArrays), c_float, POINTER(StateArrays)]),
+    "fdgs_state_place_rows_host": (c_int, [POINTER(Placement), c_int, c_void_p, c_int, c_uint32, POINTER(StateArrays),
+                                           POINTER(StateArrays), c_float, POINTER(StateArrays)]),
     "fdgs_state_extent": (c_int, [c_void_p, c_int, c_uint32, POINTER(StateArrays), POINTER(StateArrays), c_void_p]),
     "fdgs_state_extent_host": (c_int, [c_int, c_uint32, POINTER(StateArrays), POINTER(StateArrays), c_void_p]),
     "fdgs_state_gather": (c_int, [c_void_p, c_int, c_void_p, c_int, c_uint32, POINTER(StateArrays), POINTER(StateArrays)]),

@@ -14,6 +14,11 @@ orientations of the splats and their view-dependent colour with the model: the p
 inversely moved camera.  mode="points" is the script's own behaviour (`Placement.from_reference`): positions and scales only, so a turned
 object keeps its splats and its highlights pointing the old way.  Fields of a model whose deformation head is off do not depend on the time
 and are placed once, in `compose`.  No gradient flows through any of this.
+
+With allow_sparse=True a model may also be a `playback.SparseBaked`: its whole working state is placed once, in `compose`, and a frame
+places only its D dynamic rows, one fdgs_state_place_rows launch straight from the compact rows of the two bracketing timestamps:
+
+    scene = fdgs.compose.compose([sparse_background, baked_actor], placements, allow_sparse=True)
 """
 import math
 
@@ -190,9 +195,16 @@ class Composite:
     A SNAPSHOT like `Baked`: it refers to the baked frames of its models and holds placed copies.  Baking a model again, or changing a
     placement object afterwards, leaves it stale; compose again.
 
+    A model that is a `SparseBaked` (compose(..., allow_sparse=True)) keeps that class's guarantees inside the composite, placed: compose()
+    places all N rows of its working state once; a frame rewrites its D dynamic rows only (fdgs_state_place_rows), with the bits the dense
+    composite holds for them; its static rows hold the placed state at times[0] for good.  With tol < 0 the composite is the composite of
+    the dense bakes bit for bit; with tol = inf (D == 0) the model never launches.  The composite only READS its models: a SparseBaked's
+    working state and its `launches` are not touched, and it keeps rendering on its own as before.
+
     `models`, `placements`, `N` (all rows), `offsets[m]` / `slices[m]` (model m's rows: [offset_m, offset_m + N_m), in that model's own row
     order for everything `render` returns), `nbytes` (== compose_bytes(Ns)), `active_sh_degree` (the maximum over the models; the bands a
-    model does not have are stored as zeros), `launches` (fdgs_state_place launches so far, the static fields' in compose() included)."""
+    model does not have are stored as zeros), `launches` (fdgs_state_place and fdgs_state_place_rows launches so far, those of compose()
+    included)."""
 
     def __init__(self, models, placements, storage, arrays):
         self.models, self.placements = tuple(models), tuple(placements)
@@ -218,23 +230,45 @@ class Composite:
     def device(self):
         return self._storage.device
 
+    def _target(self, m, mask):
+        out = self._targets.get((m, mask))
+        if out is None:
+            out = self._targets[m, mask] = _state_arrays(self._arrays, mask, self.offsets[m])
+        return out
+
     def _place(self, m, mask, i, j, w):
         model = self.models[m]
         if mask == 0 or model.N == 0:
             return
-        a, b = _state_arrays(model.frames[i].arrays(), mask), _state_arrays(model.frames[j].arrays(), mask)
-        out = self._targets.get((m, mask))
-        if out is None:
-            out = self._targets[m, mask] = _state_arrays(self._arrays, mask, self.offsets[m])
         blend = i != j
-        _lib.check(_lib.lib().fdgs_state_place(_lib.stream_ptr(), self._structs[m], model.N, mask, a, b if blend else None,
-                                               float(w) if blend else 0.0, out))
+        if isinstance(model, SparseBaked):          # the D dynamic rows, from the compact rows of the two timestamps
+            if model.D == 0:
+                return
+            _lib.check(_lib.lib().fdgs_state_place_rows(_lib.stream_ptr(), self._structs[m], model.D, _lib.ptr(model.rows), model.N, mask,
+                                                        model._sources[i], model._sources[j] if blend else None,
+                                                        float(w) if blend else 0.0, self._target(m, mask)))
+        else:
+            a, b = _state_arrays(model.frames[i].arrays(), mask), _state_arrays(model.frames[j].arrays(), mask)
+            _lib.check(_lib.lib().fdgs_state_place(_lib.stream_ptr(), self._structs[m], model.N, mask, a, b if blend else None,
+                                                   float(w) if blend else 0.0, self._target(m, mask)))
+        self.launches += 1
+
+    def _place_working_state(self, m):
+        """All five fields of every row of a SparseBaked, from its working state: what its static rows and the fields whose head is off
+        hold for good.  The dynamic rows hold whatever time the model showed last; the first frame overwrites them."""
+        model = self.models[m]
+        if model.N == 0:
+            return
+        mask = _field_mask([True] * len(model.head_on))
+        _lib.check(_lib.lib().fdgs_state_place(_lib.stream_ptr(), self._structs[m], model.N, mask, _state_arrays(model._frame.arrays(), mask),
+                                               None, 0.0, self._target(m, mask)))
         self.launches += 1
 
     def state_at(self, t, interp="linear"):
         """The composite state at frame time t as a BakedFrame over this object's arrays (overwritten by the next call): per model, ONE
         fdgs_state_place launch for its time-dependent fields, straight from the two baked frames that bracket map_time(times, t,
-        placement) with the blend fused -- or no launch when that model's (i, j, w) is what its rows already hold."""
+        placement) with the blend fused -- or no launch when that model's (i, j, w) is what its rows already hold.  A SparseBaked takes
+        ONE fdgs_state_place_rows launch over its D dynamic rows instead, and none when D == 0."""
         _checked_interp(interp)
         for m, (model, pl, mask) in enumerate(zip(self.models, self.placements, self._masks)):
             if mask == 0:
@@ -263,13 +297,20 @@ class Composite:
         return through(0), through(1)
 
 
-def compose(models, placements=None, max_bytes=None):
+def compose(models, placements=None, max_bytes=None, allow_sparse=False):
     """Places `models` (a sequence of playback.Baked) in one world -> Composite.  placements[m] is a Placement or None (the identity);
     placements=None leaves every model where it is.  The composite owns ONE placed state of sum(N) rows: five arrays, each starting on a
     playback.SLOT_ALIGN_FLOATS boundary, model m in rows [offset_m, offset_m + N_m).  Fields whose head is off in a model do not depend on
-    the time and are placed here, once; the others per frame (Composite.state_at).  Raises TypeError for a model that is not a Baked (a
-    playback.SparseBaked has no per-timestamp frames to place), ValueError for models on different devices,
-    MemoryError -- before anything is allocated -- when `max_bytes` is given and compose_bytes(...) exceeds it."""
+    the time and are placed here, once; the others per frame (Composite.state_at).
+
+    allow_sparse=True accepts any mix of Baked and playback.SparseBaked.  A sparse model's whole working state -- all five fields, all N
+    rows -- is placed here, in one launch; a frame then places its D dynamic rows only (the guarantees are listed under `Composite`).  The
+    opt-in is deliberate: such a composite inherits the tolerance band of its sparse models and is the dense composite bit for bit only
+    where tol < 0.  compose_bytes and max_bytes are the same: the placed state has the same size.
+
+    Raises TypeError for a model that is not a Baked (a playback.SparseBaked has no per-timestamp frames to place and needs
+    allow_sparse=True), ValueError for models on different devices, MemoryError -- before anything is allocated -- when `max_bytes` is
+    given and compose_bytes(...) exceeds it."""
     models = list(models)
     if not models:
         raise ValueError("compose: at least one model")
@@ -279,9 +320,12 @@ def compose(models, placements=None, max_bytes=None):
     if len(placements) != len(models) or not all(isinstance(p, Placement) for p in placements):
         raise ValueError("compose: one Placement (or None) per model")
     for m in models:
-        if isinstance(m, SparseBaked) or not hasattr(m, "frames"):
-            raise TypeError(f"compose: a model must be a playback.Baked (dense per-timestamp frames), not {type(m).__name__}; "
-                            "composites of sparse bakes are not supported")
+        if isinstance(m, SparseBaked):
+            if not allow_sparse:
+                raise TypeError("compose: a model must be a playback.Baked (dense per-timestamp frames), not SparseBaked; "
+                                "pass allow_sparse=True to place sparse bakes (the composite then inherits their tolerance band)")
+        elif not hasattr(m, "frames"):
+            raise TypeError(f"compose: a model must be a playback.Baked (dense per-timestamp frames), not {type(m).__name__}")
     device = models[0].device
     if any(m.device != device for m in models):
         raise ValueError("compose: every model must be on the same device")
@@ -296,5 +340,8 @@ def compose(models, placements=None, max_bytes=None):
         arrays = [v[0] for v in _carve(_field_slots(total), storage)[1]]
         scene = Composite(models, placements, storage, arrays)
         for m, model in enumerate(models):
-            scene._place(m, _field_mask([not on for on in model.head_on]), 0, 0, 0.0)
+            if isinstance(model, SparseBaked):
+                scene._place_working_state(m)
+            else:
+                scene._place(m, _field_mask([not on for on in model.head_on]), 0, 0, 0.0)
     return scene

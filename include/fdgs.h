@@ -572,6 +572,27 @@ int fdgs_state_place(void* stream, const fdgs_placement* p, int N, unsigned fiel
                      const fdgs_state_arrays* b, float w, const fdgs_state_arrays* out);
 int fdgs_state_place_host(const fdgs_placement* p, int N, unsigned field_mask, const fdgs_state_arrays* a,
                           const fdgs_state_arrays* b, float w, const fdgs_state_arrays* out);
+/* Placing a SPARSE bake (addition to ABI 6; no existing signature changed): fdgs_state_scatter and fdgs_state_place in one launch, for a
+ * model of which only D of its N rows move (fdgs.playback.bake_sparse inside fdgs.compose).  For r = 0 .. D-1: row r of the COMPACT arrays
+ * a ([D, width]) -- blended with row r of b at weight w when b != NULL -- is placed by p and written to row rows[r] of out; `out` points
+ * at row 0 of the model's N rows inside the composite, as for fdgs_state_place.  Rows of out that are not listed and fields that are not
+ * selected are not touched.  The listed rows hold, bit for bit, what fdgs_state_place(p, D, field_mask, a, b, w, tmp) writes to tmp,
+ * row r moved to row rows[r]: the same functions of csrc/compose_ops.h, nothing else.
+ *
+ *   rows        a device int32[D], 4-byte aligned, STRICTLY ASCENDING, every entry in [0, N) (the list of the sparse playback entry points)
+ *   alignment   every array 4-byte aligned, the rotations and SH of a and b 16-byte aligned; out needs 4 bytes only.  Every row of
+ *               out.shs has the alignment of out.shs (192 bytes a row): 16-byte aligned it is stored as float4 pieces, else float by float
+ *
+ * D = 0, N = 0 or field_mask = 0 succeed without a launch; otherwise ONE launch on `stream`, row name "state_place_rows" in
+ * fdgs_timing_report.  FDGS_E_INVALID with a message, before anything is launched or written: what fdgs_state_place refuses (placement,
+ * field_mask, w, NULL or misaligned arrays of a selected field), D < 0, N < 0, D > N, rows == NULL or misaligned.  The device entry
+ * point cannot inspect `rows`: the kernel compares every index, as an unsigned number, against N and SKIPS a row that fails, so a bad
+ * list cannot store out of bounds -- what it does store is unspecified.  The *_host twin takes host pointers of any alignment, validates
+ * the list (range, strictly ascending) and returns FDGS_E_INVALID without writing anything. */
+int fdgs_state_place_rows(void* stream, const fdgs_placement* p, int D, const int32_t* rows, int N, unsigned field_mask,
+                          const fdgs_state_arrays* a, const fdgs_state_arrays* b, float w, const fdgs_state_arrays* out);
+int fdgs_state_place_rows_host(const fdgs_placement* p, int D, const int32_t* rows, int N, unsigned field_mask,
+                               const fdgs_state_arrays* a, const fdgs_state_arrays* b, float w, const fdgs_state_arrays* out);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Sparse baked playback (additions to ABI 6; no existing signature changed): a baked sequence that keeps ONE full state and, per
