@@ -180,6 +180,10 @@ SYMBOLS = {
                                    POINTER(StateArrays)]),
     "fdgs_state_scatter_host": (c_int, [c_int, c_void_p, c_int, c_uint32, POINTER(StateArrays), POINTER(StateArrays), c_float,
                                         POINTER(StateArrays)]),
+    "fdgs_motion_rows": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int]),
+    "fdgs_motion_rows_host": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int]),
+    "fdgs_motion_resolve": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "fdgs_motion_resolve_host": (c_int, [c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
 }
 CURVES = {"hilbert": 0, "morton": 1}      # FDGS_CURVE_*
 RGB8_MODES = {"trunc": 0, "round": 1}     # FDGS_RGB8_*

@@ -28,8 +28,8 @@ import torch
 from . import _lib
 from . import deformation as _deformation
 from . import sh as _sh
-from .playback import (BakedFrame, SparseBaked, _carve, _checked_interp, _field_mask, _field_slots, _locate, _perm_maps, _render_state,
-                       _state_arrays)
+from .playback import (_MOTION_DOC, BakedFrame, SparseBaked, _carve, _checked_interp, _field_mask, _field_slots, _locate, _perm_maps,
+                       _render_motion_state, _render_state, _state_arrays)
 
 WRAPS = ("clamp", "loop", "pingpong")
 _SH_ZERO = 1e-13        # entries of a band matrix below this are structural zeros of the rotation (the solve leaves ~1e-16 there)
@@ -225,6 +225,7 @@ class Composite:
         self._masks = [_field_mask(m.head_on) for m in self.models]         # per model: its time-dependent fields
         self._maps = self._row_maps()
         self._targets = {}          # (m, mask) -> the fdgs_state_arrays of model m's rows: they never change, filled on first use
+        self._motion_bufs = None
 
     @property
     def device(self):
@@ -285,6 +286,15 @@ class Composite:
         of models stored through a permutation are scattered back); `override_color` is [sum(N), 3] in the same order."""
         return _render_state("Composite.render", lambda t: self.state_at(t, interp), self.active_sh_degree, self.device, *self._maps,
                              viewpoint_camera, pipe, bg_color, scaling_modifier, override_color, cam_type, rgb8)
+
+    def render_motion(self, viewpoint_camera, pipe, bg_color, toward=None, toward_time=None, scaling_modifier=1.0, cam_type=None,
+                      interp="linear", min_alpha=0.0, rgb8=None):
+        return _render_motion_state("Composite.render_motion", self, lambda t: self.state_at(t, interp), self.active_sh_degree, self.device,
+                                    *self._maps, viewpoint_camera, pipe, bg_color, toward, toward_time, scaling_modifier, cam_type, min_alpha,
+                                    rgb8)
+
+    render_motion.__doc__ = _MOTION_DOC + """
+        Both times go through every model's own map_time; the motion of a placed model includes its placement."""
 
     def _row_maps(self):
         """playback._perm_maps for the whole scene: model m's rows, `slices[m]`, go through model m's own permutation."""

@@ -22,6 +22,11 @@ Where much of the set hardly moves, `bake_sparse(gaussians, times, tol)` keeps O
 values leave a tolerance band around their values at times[0]; `motion_extent` reports per row how far they go, `sparse_bake_bytes` is
 the exact stored size.  `SparseBaked.render` has the contract of `Baked.render`; a frame at a new time is one fdgs_state_scatter launch
 over the dynamic rows.
+
+`render_motion` (Baked, SparseBaked, compose.Composite) is `render` plus per-pixel motion vectors toward another frame and the accumulated
+alpha, for one extra blend pass over the frame's own sorted lists (csrc/motion.hip):
+
+    out = baked.render_motion(cam, pipe, background, toward=previous_cam)     # out["motion"] [2,H,W] pixels, out["alpha"] [1,H,W]
 """
 import bisect
 import math
@@ -155,22 +160,86 @@ def _render_state(who, frame_at, sh_degree, device, to_stored, to_model, viewpoi
         raise NotImplementedError(f"{who}: pipe.compute_cov3D_python / pipe.convert_SHs_python need the live model; use fdgs.render")
     with torch.no_grad():
         raster_settings, frame_time = _renderer._frame_settings(viewpoint_camera, cam_type, bg_color, scaling_modifier, sh_degree, device, pipe)
+        return _state_frame(frame_at(frame_time), raster_settings, to_stored, to_model, override_color, rgb8)[0]
+
+
+def _state_frame(st, raster_settings, to_stored, to_model, override_color, rgb8):
+    """(result dict, RasterState) of the forward-only frame of the BakedFrame `st`: what _render_state returns, and what it leaves behind."""
+    shs, colors = st.shs, None
+    if override_color is not None:
+        shs, colors = None, override_color.detach().float()
+        if to_stored is not None:
+            colors = to_stored(colors)
+    image, radii, depth, rstate = _rasterizer.rasterize_forward(raster_settings, st.xyz, shs, colors, st.opacity, st.scales, st.rotations,
+                                                                None, expect_backward=False)
+    vis = rstate.visibility
+    if to_model is not None:
+        radii = to_model(radii)
+        vis = radii > 0
+    out = {"render": image, "viewspace_points": None, "visibility_filter": vis, "radii": radii, "depth": depth}
+    if rgb8 is not None:
+        out["rgb8"] = to_rgb8(image, rgb8)
+    return out, rstate
+
+
+def _render_motion_state(who, owner, frame_at, sh_degree, device, to_stored, to_model, viewpoint_camera, pipe, bg_color, toward, toward_time,
+                         scaling_modifier, cam_type, min_alpha, rgb8):
+    """The body of Baked.render_motion, SparseBaked.render_motion and Composite.render_motion: the frame of _render_state, then ONE more
+    blend over the frame's own sorted lists with the per-row screen-space motion as the colour (include/fdgs.h at fdgs_geom_field: recC may
+    be rewritten between two fdgs_render_fwd calls of a forward-only frame), then the per-pixel resolve.  `owner` keeps the [N,3] copy of
+    the toward positions and the three zeros of the second blend's background (allocated on first use, not counted in nbytes)."""
+    if toward is None and toward_time is None:
+        raise ValueError(f"{who}: give `toward` (a camera: its pose and its time), `toward_time`, or both")
+    if pipe.compute_cov3D_python or pipe.convert_SHs_python:
+        raise NotImplementedError(f"{who}: pipe.compute_cov3D_python / pipe.convert_SHs_python need the live model; use fdgs.render")
+    with torch.no_grad():
+        raster_settings, frame_time = _renderer._frame_settings(viewpoint_camera, cam_type, bg_color, scaling_modifier, sh_degree, device, pipe)
+        to_settings, t_to = raster_settings, frame_time
+        if toward is not None:
+            to_settings, t_to = _renderer._frame_settings(toward, cam_type, bg_color, scaling_modifier, sh_degree, device, pipe)
+            if (int(to_settings.image_width), int(to_settings.image_height)) != (int(raster_settings.image_width), int(raster_settings.image_height)):
+                raise ValueError(f"{who}: the `toward` camera must have the image size of the frame's camera")
+        if toward_time is not None:
+            t_to = float(toward_time)
+        L = _lib.lib()
+        N = owner.N
+        if owner._motion_bufs is None:
+            owner._motion_bufs = (torch.empty(N, 3, dtype=torch.float32, device=device), torch.zeros(3, dtype=torch.float32, device=device))
+        xyz_to, zero_bg = owner._motion_bufs
+        xyz_to.copy_(frame_at(t_to).xyz)          # (the next state_at may overwrite the scratch / working state this one lives in)
         st = frame_at(frame_time)
-        shs, colors = st.shs, None
-        if override_color is not None:
-            shs, colors = None, override_color.detach().float()
-            if to_stored is not None:
-                colors = to_stored(colors)
-        image, radii, depth, rstate = _rasterizer.rasterize_forward(raster_settings, st.xyz, shs, colors, st.opacity, st.scales, st.rotations,
-                                                                    None, expect_backward=False)
-        vis = rstate.visibility
-        if to_model is not None:
-            radii = to_model(radii)
-            vis = radii > 0
-        out = {"render": image, "viewspace_points": None, "visibility_filter": vis, "radii": radii, "depth": depth}
-        if rgb8 is not None:
-            out["rgb8"] = to_rgb8(image, rgb8)
+        out, rstate = _state_frame(st, raster_settings, to_stored, to_model, None, rgb8)
+        p = rstate.params
+        W, H = int(p.W), int(p.H)
+        view_at, proj_at = rstate.keep[8], rstate.keep[9]
+        view_to, proj_to = _rasterizer._f32(to_settings.viewmatrix, device), _rasterizer._f32(to_settings.projmatrix, device)
+        recC = _lib.c_void_p()
+        _lib.check(L.fdgs_geom_field(_lib.ptr(rstate.geom), N, 3, recC))
+        stream = _lib.stream_ptr()
+        _lib.check(L.fdgs_motion_rows(stream, N, _lib.ptr(st.xyz), _lib.ptr(xyz_to), _lib.ptr(view_at), _lib.ptr(proj_at), _lib.ptr(view_to),
+                                      _lib.ptr(proj_to), W, H, recC, 4))
+        p2 = _lib.RasterParams.from_buffer_copy(p)
+        p2.bg, p2.acc_zero = _lib.ptr(zero_bg), None
+        raw = torch.empty(3, H, W, dtype=torch.float32, device=device)
+        # (depth does not depend on colour: the second blend writes the frame's depth over itself)
+        _lib.check(L.fdgs_render_fwd(stream, p2, _lib.ptr(rstate.geom), _lib.ptr(rstate.binning), _lib.ptr(rstate.img), rstate.capacity,
+                                     _lib.ptr(raw), _lib.ptr(out["depth"])))
+        motion = torch.empty(2, H, W, dtype=torch.float32, device=device)
+        alpha = torch.empty(1, H, W, dtype=torch.float32, device=device)
+        _lib.check(L.fdgs_motion_resolve(stream, H, W, float(min_alpha), _lib.ptr(raw), _lib.ptr(motion), _lib.ptr(alpha)))
+        out["motion_raw"], out["motion"], out["alpha"] = raw, motion, alpha
         return out
+
+
+_MOTION_DOC = """Everything `render(viewpoint_camera, pipe, bg_color, scaling_modifier, cam_type=cam_type, interp=interp, rgb8=rgb8)` returns,
+        bit for bit, plus per-pixel motion vectors and coverage at the cost of ONE extra blend pass (no second projection or sort):
+          "motion_raw" [3,H,W]  the blend of (mx, my, 1) per Gaussian over a zero background,
+          "motion"     [2,H,W]  motion_raw[:2] / motion_raw[2] where that is > min_alpha, else 0: ADD it to a pixel's coordinates in this
+                                frame to find the same surface point in the toward frame (pixels),
+          "alpha"      [1,H,W]  the accumulated alpha (1 - final_T), a copy of motion_raw[2].
+        `toward`: a camera of the same kind as `viewpoint_camera` -- its pose and its time are used (None: the same pose); `toward_time`
+        overrides the time.  At least one of the two, or ValueError; a `toward` camera of another image size: ValueError.  Times are clamped
+        and located as `render` locates them.  A Gaussian behind the near plane (view depth <= 0.2) of EITHER camera contributes (0, 0, 1)."""
 
 
 class Baked:
@@ -191,6 +260,7 @@ class Baked:
         self.N = int(frames[0].xyz.shape[0])
         self.nbytes = storage.numel() * storage.element_size()
         self._scratch, self._maps = None, _perm_maps(perm)
+        self._motion_bufs = None
 
     @property
     def device(self):
@@ -233,6 +303,14 @@ class Baked:
         "rgb8", the uint8 [H,W,3] image of to_rgb8.  The pipe's python SH / covariance paths are not available from a baked state."""
         return _render_state("Baked.render", lambda t: self.state_at(t, interp)[0], self.active_sh_degree, self.device, *self._maps,
                              viewpoint_camera, pipe, bg_color, scaling_modifier, override_color, cam_type, rgb8)
+
+    def render_motion(self, viewpoint_camera, pipe, bg_color, toward=None, toward_time=None, scaling_modifier=1.0, cam_type=None,
+                      interp="linear", min_alpha=0.0, rgb8=None):
+        return _render_motion_state("Baked.render_motion", self, lambda t: self.state_at(t, interp)[0], self.active_sh_degree, self.device,
+                                    *self._maps, viewpoint_camera, pipe, bg_color, toward, toward_time, scaling_modifier, cam_type, min_alpha,
+                                    rgb8)
+
+    render_motion.__doc__ = _MOTION_DOC
 
 
 def bake(pc, times, max_bytes=None):
@@ -376,6 +454,7 @@ class SparseBaked:
         self._sources, self._target = [_state_arrays(c, self._mask) for c in compact], _state_arrays(arrays, self._mask)
         self._maps = _perm_maps(perm)
         self._shown = (0, 0, 0.0)               # the (i, j, w) the dynamic rows of the working state hold
+        self._motion_bufs = None
 
     @property
     def device(self):
@@ -399,6 +478,15 @@ class SparseBaked:
         """The contract of `Baked.render`, on the state `state_at` gives."""
         return _render_state("SparseBaked.render", lambda t: self.state_at(t, interp)[0], self.active_sh_degree, self.device,
                              *self._maps, viewpoint_camera, pipe, bg_color, scaling_modifier, override_color, cam_type, rgb8)
+
+    def render_motion(self, viewpoint_camera, pipe, bg_color, toward=None, toward_time=None, scaling_modifier=1.0, cam_type=None,
+                      interp="linear", min_alpha=0.0, rgb8=None):
+        return _render_motion_state("SparseBaked.render_motion", self, lambda t: self.state_at(t, interp)[0], self.active_sh_degree,
+                                    self.device, *self._maps, viewpoint_camera, pipe, bg_color, toward, toward_time, scaling_modifier,
+                                    cam_type, min_alpha, rgb8)
+
+    render_motion.__doc__ = _MOTION_DOC + """
+        Two state_at calls: up to two fdgs_state_scatter launches; the working state ends at the frame's time, as after `render`."""
 
 
 def bake_sparse(pc, times, tol, max_bytes=None):

@@ -196,7 +196,15 @@ int fdgs_mark_visible(void* stream, int P, const float* means3D, const float* vi
  * 0 depth f32[P]; 1 recA float4[P] (x,y,conic.xx,conic.xy); 2 recB float4[P] (conic.yy,opacity,depth,0);
  * 3 recC float4[P] (r,g,b,0); 4 cov3D f32[P,6]; 5 tiles_touched u32[P]; 6 clamped u32[P] (bit c = channel c);
  * 7 rect u32[P,2] (xmin|ymin<<16, xmax|ymax<<16); 8 sorted Gaussian ids u32[P]; 9 point_offsets u32[P] (inclusive, depth
- * order; ABI 5: LOCAL to chunks of 4096 Gaussians -- the pair expansion adds the totals of the chunks in front itself). */
+ * order; ABI 5: LOCAL to chunks of 4096 Gaussians -- the pair expansion adds the totals of the chunks in front itself).
+ *
+ * Field 3 (recC) may be REWRITTEN between two fdgs_render_fwd calls of a FORWARD-ONLY frame: a frame queued with acc_zero == NULL that
+ * no fdgs_raster_bwd will follow.  recC is the only thing the blend reads that depends on colour, the blend is linear in it and never
+ * clamps it, so a second fdgs_render_fwd blends whatever three per-Gaussian values now stand there over the very same sorted lists
+ * (what the motion pass does: fdgs_motion_rows writes straight into recC).  The second call must get the same geom, binning and img and
+ * the num_rendered the buffers were laid out for; it gets its own out_color and a background of zeros (a copy of the params whose bg
+ * points at three device zeros and whose acc_zero is NULL).  It leaves final_T, n_contrib, the ranges and the tile order as they were --
+ * those decisions do not depend on colour -- and writes to out_depth the depth the first call wrote. */
 int fdgs_geom_field(void* geom, int P, int which, void** ptr);
 /* 0 sorted pair Gaussian ids u32[R]; 1 sorted pair tile ids u32[R]. */
 int fdgs_binning_field(void* binning, uint32_t num_rendered, int W, int H, int which, void** ptr);
@@ -631,6 +639,28 @@ int fdgs_state_scatter(void* stream, int D, const int32_t* rows, int N, unsigned
                        const fdgs_state_arrays* b, float w, const fdgs_state_arrays* out);
 int fdgs_state_scatter_host(int D, const int32_t* rows, int N, unsigned field_mask, const fdgs_state_arrays* a,
                             const fdgs_state_arrays* b, float w, const fdgs_state_arrays* out);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Motion vectors and coverage (additions to ABI 6; no existing signature changed): the two small launches around ONE extra blend pass of
+ * a finished forward-only frame (csrc/motion.hip, fdgs.playback.Baked.render_motion; see fdgs_geom_field for why the second
+ * fdgs_render_fwd is valid).  The arithmetic is host/device functions of csrc/motion_ops.h compiled without contraction: every *_host
+ * twin returns, over host arrays, bit for bit what the device writes.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* Row n of `out` = (mx, my, 1): where the point xyz_at[n], seen through (view_at, proj_at), is in the image of (view_toward, proj_toward)
+ * once it has moved to xyz_toward[n], minus where it is now, in pixels of a W x H image (the rasterizer's pixel convention).  ADD it to a
+ * pixel's coordinates in this frame to find the same surface point in the toward frame.  A row whose view-space depth is <= 0.2 (the
+ * rasterizer's near cull) in EITHER view gets (0, 0, 1).  The third float is always 1: blended, it is the coverage.
+ * out_stride = 3 or 4 floats per row; with 4 the fourth float is written as +0 (a recC record).  xyz_* and out need 4-byte alignment
+ * only (row slices are fine); a 16-byte aligned out with stride 4 is written one float4 per row.  The four matrices are [16] each, device.
+ * N = 0 succeeds without a launch, otherwise ONE launch; FDGS_E_INVALID with a message for a NULL pointer, N < 0, another stride, W or H < 1. */
+int fdgs_motion_rows(void* stream, int N, const float* xyz_at, const float* xyz_toward, const float* view_at, const float* proj_at,
+                     const float* view_toward, const float* proj_toward, int W, int H, float* out, int out_stride);
+int fdgs_motion_rows_host(int N, const float* xyz_at, const float* xyz_toward, const float* view_at, const float* proj_at,
+                          const float* view_toward, const float* proj_toward, int W, int H, float* out, int out_stride);
+/* raw [3,H,W] = the blend of the rows above over a zero background.  Per pixel, with a = raw[2]: motion [2,H,W] = raw[0..1] / a where
+ * a > min_alpha, 0 elsewhere (a NaN a gives zeros); alpha [1,H,W] = a, a copy.  One launch. */
+int fdgs_motion_resolve(void* stream, int H, int W, float min_alpha, const float* raw, float* motion, float* alpha);
+int fdgs_motion_resolve_host(int H, int W, float min_alpha, const float* raw, float* motion, float* alpha);
 
 #ifdef __cplusplus
 }
