@@ -108,6 +108,10 @@ class StateArrays(Structure):
     _fields_ = [("xyz", c_void_p), ("scales", c_void_p), ("rotations", c_void_p), ("opacity", c_void_p), ("shs", c_void_p)]
 
 
+class PickOut(Structure):
+    _fields_ = [("pick_id", c_void_p), ("pick_weight", c_void_p), ("surface_id", c_void_p), ("surface_depth", c_void_p)]
+
+
 # every symbol include/fdgs.h declares: (restype, argtypes)
 SYMBOLS = {
     "fdgs_last_error": (c_char_p, []),
@@ -184,6 +188,7 @@ SYMBOLS = {
     "fdgs_motion_rows_host": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int]),
     "fdgs_motion_resolve": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "fdgs_motion_resolve_host": (c_int, [c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "fdgs_render_pick": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_uint32, c_float, c_void_p, POINTER(PickOut)]),
 }
 CURVES = {"hilbert": 0, "morton": 1}      # FDGS_CURVE_*
 RGB8_MODES = {"trunc": 0, "round": 1}     # FDGS_RGB8_*

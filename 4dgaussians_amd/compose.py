@@ -28,8 +28,8 @@ import torch
 from . import _lib
 from . import deformation as _deformation
 from . import sh as _sh
-from .playback import (_MOTION_DOC, BakedFrame, SparseBaked, _carve, _checked_interp, _field_mask, _field_slots, _locate, _perm_maps,
-                       _render_motion_state, _render_state, _state_arrays)
+from .playback import (_MOTION_DOC, _PICK_DOC, BakedFrame, SparseBaked, _carve, _checked_interp, _field_mask, _field_slots, _locate,
+                       _perm_maps, _render_motion_state, _render_pick_state, _render_state, _state_arrays)
 
 WRAPS = ("clamp", "loop", "pingpong")
 _SH_ZERO = 1e-13        # entries of a band matrix below this are structural zeros of the rotation (the solve leaves ~1e-16 there)
@@ -226,6 +226,7 @@ class Composite:
         self._maps = self._row_maps()
         self._targets = {}          # (m, mask) -> the fdgs_state_arrays of model m's rows: they never change, filled on first use
         self._motion_bufs = None
+        self._pick_row_map = None
 
     @property
     def device(self):
@@ -295,6 +296,33 @@ class Composite:
 
     render_motion.__doc__ = _MOTION_DOC + """
         Both times go through every model's own map_time; the motion of a placed model includes its placement."""
+
+    def render_pick(self, viewpoint_camera, pipe, bg_color, scaling_modifier=1.0, cam_type=None, interp="linear", alpha_cut=0.5, rgb8=None):
+        return _render_pick_state("Composite.render_pick", self, lambda t: self.state_at(t, interp), self.active_sh_degree, self.device,
+                                  *self._maps, viewpoint_camera, pipe, bg_color, scaling_modifier, cam_type, alpha_cut, rgb8)
+
+    render_pick.__doc__ = _PICK_DOC + """
+        The ids are rows of the whole scene (sum(N), model m's at `slices[m]`): `model_of_rows` splits them into (model, row)."""
+
+    def _make_pick_row_map(self):
+        """The stored -> scene row map of fdgs_render_pick: model m's segment is offset_m + perm_m (offset_m + arange for a model stored in
+        its own order); None when no model is stored through a permutation."""
+        if all(m.perm is None for m in self.models):
+            return None
+        segs = [(torch.arange(m.N, dtype=torch.int32, device=self.device) if m.perm is None else m.perm.to(torch.int32)) + o
+                for m, o in zip(self.models, self.offsets)]
+        return torch.cat(segs).to(torch.int32).contiguous()
+
+    def model_of_rows(self, ids):
+        """(model, row), int32 tensors of the shape of `ids` (rows of the scene, e.g. "pick_id" of render_pick): the index into `models`
+        and the row inside that model, in its own order; both -1 where ids is -1."""
+        ids = ids.to(torch.int64)
+        starts = torch.tensor(self.offsets, dtype=torch.int64, device=ids.device)
+        model = torch.bucketize(ids, starts, right=True) - 1          # the last model whose first row is <= id (empty models are skipped over)
+        hit = ids >= 0
+        model = torch.where(hit, model, torch.full_like(model, -1))
+        row = torch.where(hit, ids - starts[model.clamp_min(0)], torch.full_like(ids, -1))
+        return model.to(torch.int32), row.to(torch.int32)
 
     def _row_maps(self):
         """playback._perm_maps for the whole scene: model m's rows, `slices[m]`, go through model m's own permutation."""

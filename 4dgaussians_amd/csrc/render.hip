@@ -8,6 +8,8 @@
 // backward of rounds 1-2 (four waves meeting in LDS slots) stays selectable (tuning knob rbwd_ppl = 0; 2 = two waves per tile with two
 // pixels per lane): the three forms are compared with each other in tests/test_gpu_raster.py.  (A strip form of the FORWARD measured
 // slower and was dropped in round 3.)
+// Pick pass (render_pick_kernel): the forward's layout once more over a finished frame's lists, for the id of the Gaussian with the largest
+// blend weight and the id and depth of the one at which the accumulated alpha reaches a cut; it writes nothing into the frame.
 // Tile rows are dealt to the XCDs in groups (unit_of_block: workgroup b runs on XCD b % 8), so that neighbouring tiles -- which list
 // the same Gaussians -- share an XCD's 4 MiB L2 and every XCD owns rows from the whole height of the image.
 // Replaces renderCUDA forward/backward of the un-vendored rasterizer (Appendix B.3/B.4).
@@ -214,6 +216,101 @@ __global__ void __launch_bounds__(256) render_fwd_kernel(RenderArgs a) {
             uint32_t q = sTodo[0]; q = sTodo[1] > q ? sTodo[1] : q; q = sTodo[2] > q ? sTodo[2] : q; q = sTodo[3] > q ? sTodo[3] : q;
             a.tile_todo[tile] = q;
         }
+    }
+}
+
+// ---- the pick pass: which Gaussian a pixel shows, and the depth at which it turns opaque ----------------------------------------------
+// One more walk over the lists of a FINISHED frame, front to back, up to each pixel's n_contrib, taking the decisions render_fwd_kernel
+// took: the same expressions for the power, alpha, w = alpha * T and T, so w has the bits of the forward's w (the forward contracts only
+// its colour sums, which do not exist here; this kernel is compiled without contraction so that A += alpha * T stays a product and a sum,
+// the float32 running sum a blended colour channel of ones accumulates).  The layout is the forward's: one workgroup per tile in the
+// forward's own tile order (read, not rebuilt), 256 entries staged per round through LDS -- recA, recB and this time the ids, recC is
+// not read --, ids two rounds ahead and records one round ahead in registers.  Per lane: T, A, the largest w and its id, the id and depth
+// of the entry at which A reached alpha_cut.  Nothing of the frame is written: no atomics, the four images are the only stores.
+struct PickArgs : BlendHead {
+    const uint32_t* tile_todo;               // per tile: max n_contrib, the forward's walk length
+    const uint2* ranges; const uint32_t* pair_gid;
+    const float4 *recA, *recB, *recC;
+    const float* bg;
+    const float* final_T; const uint32_t* n_contrib;
+    uint32_t R; int P;                       // what the lists were laid out for: fences for a stale img
+    int empty;                               // 1: no Gaussians or no pairs, every pixel gets -1 / +0 and nothing of the frame is read
+    float alpha_cut;
+    const int32_t* row_map;                  // opt [P]: the id written for Gaussian g
+    int32_t* pick_id; float* pick_weight; int32_t* surface_id; float* surface_depth;      // each opt
+};
+
+__global__ void __launch_bounds__(256) render_pick_kernel(PickArgs a) {
+#pragma clang fp contract(off)
+    const int tile = a.empty ? unit_of_block(blockIdx.x, a.gx, a.gy, 1, a.bh) : unit_lookup(a.order, a.per_xcd, blockIdx.x, a.gx, a.gy, 1, a.bh);
+    if (tile < 0 || tile >= a.gx * a.gy) return;
+    __shared__ float4 sA[256], sB[256];
+    __shared__ uint32_t sG[256];
+    const int t = threadIdx.x;
+    const int x = (tile % a.gx) * TILE + (t & 15), y = (tile / a.gx) * TILE + (t >> 4);
+    const bool inside = x < a.W && y < a.H;
+    const float pxf = (float)x, pyf = (float)y;
+    const size_t pix = (size_t)y * a.W + x;
+    uint2 range = make_uint2(0u, 0u);
+    uint32_t walk = 0u, own = 0u;
+    if (!a.empty) {
+        range = a.ranges[tile];
+        range.y = range.y < a.R ? range.y : a.R;
+        range.x = range.x < range.y ? range.x : range.y;
+        walk = a.tile_todo[tile];
+        own = inside ? a.n_contrib[pix] : 0u;
+    }
+    const int n_list = (int)(range.y - range.x);
+    const int todo = walk < (uint32_t)n_list ? (int)walk : n_list;           // the tile's walk length ...
+    const int mine = own < (uint32_t)n_list ? (int)own : n_list;            // ... and this lane's, both clamped to the list
+    const int rounds = (todo + 255) / 256;
+    float T = 1.0f, A = 0.0f, best_w = 0.0f, s_depth = 0.0f;
+    uint32_t best_g = 0xFFFFFFFFu, s_g = 0xFFFFFFFFu;
+    int seen = 0;                            // entries of the list this lane has passed
+    auto gid_of = [&](int r) -> uint32_t {
+        const int e = r * 256 + t;
+        return a.pair_gid[range.x + (e < n_list ? e : n_list - 1)];
+    };
+    uint32_t g_cur = 0u, g_nxt = 0u;
+    float4 rA, rB;
+    if (rounds > 0) {
+        g_cur = gid_of(0);
+        if (rounds > 1) g_nxt = gid_of(1);
+        rA = a.recA[g_cur]; rB = a.recB[g_cur];
+    }
+    for (int r = 0; r < rounds; r++) {
+        if (__syncthreads_count(seen >= mine) == 256) break;
+        sA[t] = rA; sB[t] = rB; sG[t] = g_cur;
+        __syncthreads();
+        if (r + 1 < rounds) { g_cur = g_nxt; rA = a.recA[g_cur]; rB = a.recB[g_cur]; }
+        if (r + 2 < rounds) g_nxt = gid_of(r + 2);
+        const int rem = mine - seen;
+        const int lim = rem < 256 ? rem : 256;
+        for (int j = 0; j < lim; j++) {
+            const float4 Aj = sA[j];
+            const float4 B = sB[j];
+            const float dx = Aj.x - pxf, dy = Aj.y - pyf;
+            const float power = blend_power(blend_power_xx(Aj.z, dx), blend_power_xy(Aj.w, dx), B.x, dy);
+            if (power > 0.0f) continue;
+            const float alpha = fminf(FDGS_ALPHA_MAX, B.y * __expf(power));
+            if (alpha < FDGS_ALPHA_MIN) continue;
+            const float w = alpha * T;
+            A = A + w;
+            if (w > best_w) { best_w = w; best_g = sG[j]; }                  // (strictly: on a tie the entry in front stays)
+            if (s_g == 0xFFFFFFFFu && A >= a.alpha_cut) { s_g = sG[j]; s_depth = B.z; }
+            T = T * (1.0f - alpha);
+        }
+        seen += 256;
+    }
+    if (inside) {
+        auto id_of = [&](uint32_t g) -> int32_t {
+            if (g >= (uint32_t)a.P) return -1;
+            return a.row_map ? a.row_map[g] : (int32_t)g;
+        };
+        if (a.pick_id) a.pick_id[pix] = id_of(best_g);
+        if (a.pick_weight) a.pick_weight[pix] = best_w;
+        if (a.surface_id) a.surface_id[pix] = id_of(s_g);
+        if (a.surface_depth) a.surface_depth[pix] = s_depth;
     }
 }
 
@@ -643,7 +740,35 @@ extern "C" int fdgs_render_fwd(void* stream_, const fdgs_raster_params* p, const
     return FDGS_OK;
 }
 
-extern "C" int fdgs_raster_bwd(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning,
+extern "C" int fdgs_render_pick(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
+                                uint32_t R, float alpha_cut, const int32_t* row_map_opt, const fdgs_pick_out* out) {
+    FDGS_REQUIRE(p && geom && binning && img && out, "NULL pointer (params, geom, binning, img and out)");
+    FDGS_REQUIRE(p->P >= 0 && p->W >= 1 && p->H >= 1, "bad P/W/H");
+    FDGS_REQUIRE((p->W + TILE - 1) / TILE < 65536 && (p->H + TILE - 1) / TILE < 65536, "image too large");
+    FDGS_REQUIRE(alpha_cut > 0.0f && alpha_cut <= 1.0f, "bad alpha_cut (in (0, 1]; a NaN is refused)");
+    FDGS_REQUIRE(out->pick_id || out->pick_weight || out->surface_id || out->surface_depth, "NULL pointer (at least one output)");
+    FDGS_REQUIRE(aligned_to(out->pick_id, 4) && aligned_to(out->pick_weight, 4) && aligned_to(out->surface_id, 4) &&
+                     aligned_to(out->surface_depth, 4) && aligned_to(row_map_opt, 4), "arrays must be 4-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    PickArgs a{};
+    const ImgLayout il = fill_blend_args(a, p, geom, binning, img, R);
+    a.tile_todo = at<uint32_t>(img, il.todo);
+    a.R = R; a.P = p->P;
+    a.empty = (p->P == 0 || R == 0) ? 1 : 0;
+    a.alpha_cut = alpha_cut; a.row_map = row_map_opt;
+    a.pick_id = out->pick_id; a.pick_weight = out->pick_weight; a.surface_id = out->surface_id; a.surface_depth = out->surface_depth;
+    // the forward's own heaviest-first order, where fdgs_render_fwd wrote one (make_tile_order's condition); never rebuilt here
+    const bool ordered = !a.empty && g_tune.tile_order && il.per_xcd <= TILE_ORDER_MAX && il.per_xcd >= 1;
+    a.order = ordered ? at<uint32_t>(img, il.order_f) : nullptr;
+    {
+        FDGS_TIMED("render_pick", stream);
+        hipLaunchKernelGGL(render_pick_kernel, dim3(unit_grid(a.gx, a.gy, 1, a.bh)), dim3(256), 0, stream, a);
+    }
+    FDGS_LAUNCH_CHECK("render_pick", p->debug, stream);
+    return FDGS_OK;
+}
+
+extern "C" int fdgs_raster_bwd(void* stream_,const fdgs_raster_params* p, const void* geom, const void* binning,
                                const void* img, uint32_t R, const fdgs_raster_grads* g) {
     int rc = validate_raster_params(p);
     if (rc) return rc;

@@ -27,6 +27,13 @@ over the dynamic rows.
 alpha, for one extra blend pass over the frame's own sorted lists (csrc/motion.hip):
 
     out = baked.render_motion(cam, pipe, background, toward=previous_cam)     # out["motion"] [2,H,W] pixels, out["alpha"] [1,H,W]
+
+`render_pick` (the same three classes) is `render` plus what is under every pixel -- the row of the Gaussian that dominates it, and the
+row and view depth of the one at which the pixel turns opaque -- for one extra walk over those lists (csrc/render.hip: render_pick_kernel);
+`unproject` takes a pixel and that depth to a world point:
+
+    out = baked.render_pick(cam, pipe, background)                            # out["pick_id"], out["surface_id"] [H,W]; out["surface_depth"] [1,H,W]
+    point = fdgs.playback.unproject(cam, torch.tensor([[x, y]]), out["surface_depth"][0, y, x].reshape(1))
 """
 import bisect
 import math
@@ -242,6 +249,78 @@ _MOTION_DOC = """Everything `render(viewpoint_camera, pipe, bg_color, scaling_mo
         and located as `render` locates them.  A Gaussian behind the near plane (view depth <= 0.2) of EITHER camera contributes (0, 0, 1)."""
 
 
+def _perm_row_map(perm):
+    """The stored -> model row map of rows stored through `perm` (stored row i is model row perm[i]) as the int32 tensor fdgs_render_pick
+    reads, or None for rows stored in the model's order."""
+    return None if perm is None else perm.to(torch.int32).contiguous()
+
+
+def _render_pick_state(who, owner, frame_at, sh_degree, device, to_stored, to_model, viewpoint_camera, pipe, bg_color, scaling_modifier,
+                       cam_type, alpha_cut, rgb8):
+    """The body of Baked.render_pick, SparseBaked.render_pick and Composite.render_pick: the frame of _render_state, then ONE
+    fdgs_render_pick over the RasterState it left behind (include/fdgs.h: one more walk over the frame's own sorted lists, which writes
+    nothing into them).  `owner` keeps the stored -> model row map (built on first use, not counted in nbytes)."""
+    if pipe.compute_cov3D_python or pipe.convert_SHs_python:
+        raise NotImplementedError(f"{who}: pipe.compute_cov3D_python / pipe.convert_SHs_python need the live model; use fdgs.render")
+    alpha_cut = float(alpha_cut)
+    if not 0.0 < alpha_cut <= 1.0:
+        raise ValueError(f"{who}: alpha_cut in (0, 1], not {alpha_cut!r}")
+    with torch.no_grad():
+        raster_settings, frame_time = _renderer._frame_settings(viewpoint_camera, cam_type, bg_color, scaling_modifier, sh_degree, device, pipe)
+        if owner._pick_row_map is None:          # (stays None for rows stored in the model's order: there is nothing to build)
+            owner._pick_row_map = owner._make_pick_row_map()
+        row_map = owner._pick_row_map
+        out, rstate = _state_frame(frame_at(frame_time), raster_settings, to_stored, to_model, None, rgb8)
+        p = rstate.params
+        W, H = int(p.W), int(p.H)
+        ids = torch.empty(2, H, W, dtype=torch.int32, device=device)
+        vals = torch.empty(2, H, W, dtype=torch.float32, device=device)
+        po = _lib.PickOut()
+        po.pick_id, po.surface_id, po.pick_weight, po.surface_depth = ids[0].data_ptr(), ids[1].data_ptr(), vals[0].data_ptr(), vals[1].data_ptr()
+        _lib.check(_lib.lib().fdgs_render_pick(_lib.stream_ptr(), p, _lib.ptr(rstate.geom), _lib.ptr(rstate.binning), _lib.ptr(rstate.img),
+                                               rstate.capacity, alpha_cut, _lib.ptr(row_map), po))
+        out["pick_id"], out["surface_id"], out["pick_weight"], out["surface_depth"] = ids[0], ids[1], vals[0], vals[1:2]
+        return out
+
+
+_PICK_DOC = """Everything `render(viewpoint_camera, pipe, bg_color, scaling_modifier, cam_type=cam_type, interp=interp, rgb8=rgb8)` returns,
+        bit for bit, plus what is under every pixel, at the cost of ONE extra walk over the frame's own sorted lists (fdgs_render_pick: no
+        second projection, sort or blend):
+          "pick_id"       int32   [H,W]    the row of the Gaussian with the largest blend weight w = alpha * T at the pixel (on a tie the
+                                           one in front); -1 where nothing contributed,
+          "pick_weight"   float32 [H,W]    that weight, the bits the frame blended the Gaussian's colour with; 0 where nothing contributed,
+          "surface_id"    int32   [H,W]    the row of the first Gaussian, front to back, with which the accumulated alpha reaches
+                                           `alpha_cut`; -1 where it never does,
+          "surface_depth" float32 [1,H,W]  that Gaussian's view depth (alpha_cut = 0.5: the median depth, a depth that lies ON a surface,
+                                           where "depth" is the alpha-weighted mean); 0 where surface_id is -1.
+        The ids follow the row order of "radii".  alpha_cut outside (0, 1]: ValueError.  `unproject` turns a pixel and its surface_depth
+        into a world point."""
+
+
+def unproject(viewpoint_camera, xy, depth, cam_type=None):
+    """World points [K,3] of the pixel coordinates `xy` [K,2] (x = column, y = row; fractions allowed) at the view depths `depth` [K], in
+    the rasterizer's pixel convention: ndc = (2 * px + 1) / W - 1, x_view = ndc_x * tanfovx * z, y_view = ndc_y * tanfovy * z, then the
+    inverse of the view matrix.  Plain torch ops on the device of `depth`; with "surface_depth" of render_pick a click becomes the point to
+    place a model at.  `viewpoint_camera`: a camera as `render` takes it (the PanopticSports dict with cam_type="PanopticSports")."""
+    if cam_type == "PanopticSports":
+        s = viewpoint_camera["camera"]
+        W, H, tanx, tany, view = int(s.image_width), int(s.image_height), float(s.tanfovx), float(s.tanfovy), s.viewmatrix
+    else:
+        W, H = int(viewpoint_camera.image_width), int(viewpoint_camera.image_height)
+        tanx, tany = math.tan(viewpoint_camera.FoVx * 0.5), math.tan(viewpoint_camera.FoVy * 0.5)
+        view = viewpoint_camera.world_view_transform
+    with torch.no_grad():
+        z = depth.detach().reshape(-1).float()
+        xy = xy.detach().reshape(-1, 2).to(device=z.device, dtype=torch.float32)
+        if xy.shape[0] != z.shape[0]:
+            raise ValueError("unproject: xy [K,2] and depth [K]")
+        view = view.detach().to(device=z.device, dtype=torch.float32)
+        nx = (2.0 * xy[:, 0] + 1.0) / W - 1.0
+        ny = (2.0 * xy[:, 1] + 1.0) / H - 1.0
+        pv = torch.stack([nx * tanx * z, ny * tany * z, z, torch.ones_like(z)], dim=1)
+        return (pv @ torch.linalg.inv(view))[:, :3]          # (row vectors: p_view = [p_world, 1] @ view, the rasterizer's layout)
+
+
 class Baked:
     """The deformed, activated state of a model at `times`, resident on the device: positions [N,3], scales [N,3] (exp applied), rotations
     [N,4] (unit quaternions), opacity [N,1] (sigmoid applied), SH [N,16,3] -- what the no-grad branch of render() hands to the rasterizer.
@@ -261,6 +340,10 @@ class Baked:
         self.nbytes = storage.numel() * storage.element_size()
         self._scratch, self._maps = None, _perm_maps(perm)
         self._motion_bufs = None
+        self._pick_row_map = None
+
+    def _make_pick_row_map(self):
+        return _perm_row_map(self.perm)
 
     @property
     def device(self):
@@ -311,6 +394,12 @@ class Baked:
                                     rgb8)
 
     render_motion.__doc__ = _MOTION_DOC
+
+    def render_pick(self, viewpoint_camera, pipe, bg_color, scaling_modifier=1.0, cam_type=None, interp="linear", alpha_cut=0.5, rgb8=None):
+        return _render_pick_state("Baked.render_pick", self, lambda t: self.state_at(t, interp)[0], self.active_sh_degree, self.device,
+                                  *self._maps, viewpoint_camera, pipe, bg_color, scaling_modifier, cam_type, alpha_cut, rgb8)
+
+    render_pick.__doc__ = _PICK_DOC
 
 
 def bake(pc, times, max_bytes=None):
@@ -455,6 +544,10 @@ class SparseBaked:
         self._maps = _perm_maps(perm)
         self._shown = (0, 0, 0.0)               # the (i, j, w) the dynamic rows of the working state hold
         self._motion_bufs = None
+        self._pick_row_map = None
+
+    def _make_pick_row_map(self):
+        return _perm_row_map(self.perm)
 
     @property
     def device(self):
@@ -487,6 +580,12 @@ class SparseBaked:
 
     render_motion.__doc__ = _MOTION_DOC + """
         Two state_at calls: up to two fdgs_state_scatter launches; the working state ends at the frame's time, as after `render`."""
+
+    def render_pick(self, viewpoint_camera, pipe, bg_color, scaling_modifier=1.0, cam_type=None, interp="linear", alpha_cut=0.5, rgb8=None):
+        return _render_pick_state("SparseBaked.render_pick", self, lambda t: self.state_at(t, interp)[0], self.active_sh_degree, self.device,
+                                  *self._maps, viewpoint_camera, pipe, bg_color, scaling_modifier, cam_type, alpha_cut, rgb8)
+
+    render_pick.__doc__ = _PICK_DOC
 
 
 def bake_sparse(pc, times, tol, max_bytes=None):

@@ -662,6 +662,39 @@ int fdgs_motion_rows_host(int N, const float* xyz_at, const float* xyz_toward, c
 int fdgs_motion_resolve(void* stream, int H, int W, float min_alpha, const float* raw, float* motion, float* alpha);
 int fdgs_motion_resolve_host(int H, int W, float min_alpha, const float* raw, float* motion, float* alpha);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Pick pass (an addition to ABI 6; no existing signature changed): which Gaussian a pixel of a finished frame shows and the depth at
+ * which the pixel turns opaque, from ONE more walk over the frame's own sorted lists (csrc/render.hip: render_pick_kernel,
+ * fdgs.playback.Baked.render_pick).  No second projection, no sort.  An argmax and a threshold crossing are not linear in a colour, so
+ * this is not a second fdgs_render_fwd (what the motion pass is) but a kernel of its own.
+ *
+ * Valid after fdgs_render_fwd, or after fdgs_raster_fwd_capacity once the frame is known to be exact (true count <= capacity), with the
+ * same geom, binning and img and the num_rendered the buffers were laid out for; a training frame or a forward-only one.  Per pixel the
+ * tile's list is walked from the front up to the pixel's n_contrib with exactly the forward's decisions -- the power, alpha =
+ * min(0.99, opacity * exp(power)), the power > 0 and alpha < 1/255 skips, w = alpha * T, T *= 1 - alpha are the forward's expressions:
+ * w has the bits of the weight the forward blended the Gaussian's colour with -- and A is the float32 running sum of w in list order
+ * (what a blended colour channel of ones accumulates).
+ * -------------------------------------------------------------------------------------------------------- */
+typedef struct fdgs_pick_out {
+    int32_t* pick_id;       /* opt [H*W]: the Gaussian with the largest w (a tie goes to the earlier list entry, the one in front); -1 where
+                               nothing contributed */
+    float*   pick_weight;   /* opt [H*W]: that w; +0 where nothing contributed */
+    int32_t* surface_id;    /* opt [H*W]: the first contributor after whose w was added A >= alpha_cut holds; -1 where A never gets there */
+    float*   surface_depth; /* opt [H*W]: that contributor's view depth (recB.z, the value the forward blends into out_depth); +0 where
+                               surface_id is -1 */
+} fdgs_pick_out;
+/* alpha_cut in (0, 1] (0.5: the median depth).  row_map_opt: device int32[P] or NULL; when given, an id g is written as row_map_opt[g]
+ * (-1 stays -1): ids in another row order than the one the rasterizer was handed.  Any output may be NULL, not all four.
+ * FDGS_E_INVALID with a message, before anything is launched, for: a NULL params, geom, binning, img or out; W or H < 1; an alpha_cut
+ * outside (0, 1] or NaN; all four outputs NULL; an output or row_map_opt that is not 4-byte aligned.  P == 0 or num_rendered == 0
+ * succeeds and writes -1 / +0 everywhere.  ONE launch on `stream`, nothing synchronises (params->debug aside); its row in
+ * fdgs_timing_report is "render_pick".
+ * It WRITES NOTHING into geom, binning or img: final_T, n_contrib, the ranges, the walk lengths and the tile orders keep their bits (the
+ * tiles are taken in the order the forward left in img field 4, which is read, not rebuilt), so a motion pass or fdgs_raster_bwd of the
+ * same frame may follow.  A stale img cannot make it read past a list: every walk is clamped to the tile's range and num_rendered. */
+int fdgs_render_pick(void* stream, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
+                     uint32_t num_rendered, float alpha_cut, const int32_t* row_map_opt, const fdgs_pick_out* out);
+
 #ifdef __cplusplus
 }
 #endif
