@@ -11,6 +11,11 @@
 // Radix pass = wave64 ballot ranking (one ballot per digit bit gives each lane its rank among equal digits), per-wave
 // digit counters in LDS, keys regrouped by digit in LDS so that the global scatter writes contiguous runs.  A sort over
 // nbits key bits runs ceil(nbits / 8) passes of near-equal digit width (32 -> 8,8,8,8; the 13-bit tile id -> 7,6).
+//
+// That chain is binning form 0 (tuning knob bin_form).  Form 1, further down, has no global sort: once every pair is placed straight into
+// its tile's slot range the only order left is by depth inside one tile, and that fits in LDS -- per-tile count, one scan of the counts
+// (= the ranges), emit, one sort per tile: the same lists bit for bit (depth bits, ties by Gaussian index) from a fill and five launches
+// instead of 21.  Form 0 stays: spatial.hip sorts with radix_sort_pairs, images of more than 16 384 tiles run it, and A/B legs need it.
 #include "common.h"
 #include "raster.h"
 
@@ -396,6 +401,318 @@ __global__ void __launch_bounds__(256) tile_ranges_kernel(const uint32_t* __rest
     }
 }
 
+// ---------------------------------------------------------------- bin_form 1: pairs placed straight into their tile's slots, one LDS sort per tile
+// No global sort: (1) tile_pairs_kernel<false> counts the pairs of every tile, (2) tile_scan_kernel turns the counts into the tiles' slot
+// ranges (= `ranges`) and clears a per-tile cursor, (3) tile_pairs_kernel<true> writes every pair's Gaussian into its tile's range in
+// arrival order, (4) tile_sort_kernel fetches the Gaussians' depths and orders each range by the 64-bit key (depth bits << 32 | Gaussian)
+// -- unique per pair, so the result does not depend on the arrival order and equals the order of the two stable sorts of form 0 (depth,
+// ties by index).
+//
+// The pairs of a Gaussian are the tiles of its square, under culling the set bits of its 256-bit mask (squares of more than 256 tiles are
+// not culled): the pair set of expand_pairs_kernel.  walk_pairs() hands every pair of a wave's 64 Gaussians to `f`: a square of up to 64
+// tiles is walked by its own lane (its mask is one 64-bit word: pop the lowest set bit), a larger one by the whole wave, 64 tiles per
+// round (the nearest Gaussians cover 60+ tiles each: one lane would keep 63 waiting).  Must be called by all lanes of the wave.
+template <typename F>
+__device__ __forceinline__ void walk_pairs(uint32_t cnt, uint2 rc, uint4 mlo, uint4 mhi, bool culled, uint32_t gx, uint32_t gid, F f) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t xmin = rc.x & 0xFFFFu, ymin = rc.x >> 16, w = (rc.y & 0xFFFFu) - xmin, h = (rc.y >> 16) - ymin;
+    const uint32_t area = cnt ? w * h : 0u;
+    const bool masked = culled && area <= 256u;
+    if (area != 0u && area <= 64u) {
+        unsigned long long m = masked ? (((unsigned long long)mlo.y << 32) | mlo.x) : (area == 64u ? ~0ull : (1ull << area) - 1ull);
+        const uint32_t inv = (65536u + w - 1u) / w;          // l / w = (l * inv) >> 16 for l < 64, w <= 64
+        const uint32_t tile0 = ymin * gx + xmin;
+        while (m) {
+            const uint32_t l = (uint32_t)__ffsll((unsigned long long)m) - 1u;
+            m &= m - 1ull;
+            const uint32_t q = (l * inv) >> 16;
+            f(tile0 + q * gx + (l - q * w), gid);
+        }
+    }
+    uint64_t big = __ballot(area > 64u);
+    while (big) {
+        const int src = __ffsll((unsigned long long)big) - 1;
+        big &= big - 1ull;
+        const uint32_t brx = __shfl(rc.x, src, 64), bry = __shfl(rc.y, src, 64), bgid = __shfl(gid, src, 64);
+        const uint32_t bx = brx & 0xFFFFu, by = brx >> 16, bw = (bry & 0xFFFFu) - bx, barea = bw * ((bry >> 16) - by);
+        if (culled && barea <= 256u) {
+            // bit l of the mask = 32-bit word l / 32, bit l % 32: round k looks at l = 64 k + lane
+            const uint32_t w0 = __shfl(mlo.x, src, 64), w1 = __shfl(mlo.y, src, 64), w2 = __shfl(mlo.z, src, 64), w3 = __shfl(mlo.w, src, 64);
+            const uint32_t w4 = __shfl(mhi.x, src, 64), w5 = __shfl(mhi.y, src, 64), w6 = __shfl(mhi.z, src, 64), w7 = __shfl(mhi.w, src, 64);
+            const bool up = lane >= 32u;
+            const uint32_t word[4] = {up ? w1 : w0, up ? w3 : w2, up ? w5 : w4, up ? w7 : w6};
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) {
+                const uint32_t l = 64u * k + lane;
+                if (l < barea && ((word[k] >> (lane & 31u)) & 1u)) {
+                    const uint32_t q = l / bw;
+                    f((by + q) * gx + bx + (l - q * bw), bgid);
+                }
+            }
+        } else {
+            for (uint32_t l = lane; l < barea; l += 64u) {
+                const uint32_t q = l / bw;
+                f((by + q) * gx + bx + (l - q * bw), bgid);
+            }
+        }
+    }
+}
+
+// A workgroup owns blockDim.x consecutive Gaussians and privatises the tiles' counters in LDS (ds_add; global atomics into a few hot cells
+// run at 5 G/s).  Count: walk, then ONE global atomic per touched tile onto the tile's counter.  Emit: the same walk, then one
+// global atomic per touched tile onto the tile's cursor claims the workgroup's slots in the tile's range; the counter becomes the first
+// claimed position, and a second walk hands out the positions (ds_add_rtn) and writes the entries.  Positions stay below 2^31: the top
+// bit marks a tile whose list was dropped (capacity mode).
+constexpr uint32_t TP_DROPPED = 0x80000000u;
+template <bool EMIT>
+__global__ void __launch_bounds__(1024) tile_pairs_kernel(int P, const uint32_t* __restrict__ tiles, const uint2* __restrict__ rect,
+                                                          const uint4* __restrict__ cullmask, const uint32_t* __restrict__ total, int gx,
+                                                          uint32_t ntiles, uint32_t* __restrict__ gcount /* count: the tiles' counters; emit: their cursors */,
+                                                          const uint2* __restrict__ ranges, uint32_t* __restrict__ ugid) {
+    extern __shared__ uint32_t s_cnt[];       // [ntiles]
+    const bool culled = total[2] != 0;
+    const uint32_t t = threadIdx.x, i = blockIdx.x * blockDim.x + t;
+    const uint32_t cnt = i < (uint32_t)P ? tiles[i] : 0u;
+    if (!__syncthreads_or(cnt != 0u)) return;              // nothing of this workgroup is on screen
+    uint2 rc = make_uint2(0u, 0u);
+    uint4 mlo = make_uint4(0u, 0u, 0u, 0u), mhi = mlo;
+    if (cnt) {
+        rc = rect[i];
+        if (culled && ((rc.y & 0xFFFFu) - (rc.x & 0xFFFFu)) * ((rc.y >> 16) - (rc.x >> 16)) <= 256u) {
+            mlo = cullmask[2 * (size_t)i]; mhi = cullmask[2 * (size_t)i + 1];
+        }
+    }
+    for (uint32_t k = t; k < ntiles; k += blockDim.x) s_cnt[k] = 0u;
+    __syncthreads();
+    walk_pairs(cnt, rc, mlo, mhi, culled, (uint32_t)gx, i, [&](uint32_t tile, uint32_t) { atomicAdd(&s_cnt[tile], 1u); });
+    __syncthreads();
+    for (uint32_t k = t; k < ntiles; k += blockDim.x) {
+        const uint32_t n = s_cnt[k];
+        if (n) {
+            if (EMIT) {
+                const uint2 r = ranges[k];     // (capacity mode: a tile whose list does not fit has the range (0, 0): its pairs are dropped)
+                s_cnt[k] = r.y ? r.x + atomicAdd(&gcount[k], n) : TP_DROPPED;
+            } else {
+                atomicAdd(&gcount[k], n);
+            }
+        }
+    }
+    if (EMIT) {
+        __syncthreads();
+        walk_pairs(cnt, rc, mlo, mhi, culled, (uint32_t)gx, i, [&](uint32_t tile, uint32_t g) {
+            const uint32_t o = atomicAdd(&s_cnt[tile], 1u);
+            if (o < TP_DROPPED) ugid[o] = g;
+        });
+    }
+}
+
+// One workgroup: exclusive scan of the tiles' pair counts = the tiles' slot ranges, written as `ranges`; empty tiles get (0, 0).  `cap`
+// (capacity mode): a tile whose range would end behind it gets (0, 0) too, and so does every tile after it (the ends never decrease): the
+// frame keeps whole tiles, in image order, while they fit.  The cursors of tile_pairs_kernel<true> start at 0.
+// 1024 threads, up to 16 consecutive tiles each (ntiles <= TILE_FORM1_MAX_TILES = 16 384): one round of loads, one scan over the threads.
+__global__ void __launch_bounds__(1024) tile_scan_kernel(const uint32_t* __restrict__ cnt, uint32_t ntiles, uint2* __restrict__ ranges,
+                                                         uint32_t* __restrict__ cursor, uint32_t cap) {
+    __shared__ uint32_t wsum[16];
+    const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const uint32_t items = (ntiles + 1023u) >> 10, i0 = t * items;
+    uint32_t v[16], sum = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 16; k++) {
+        v[k] = (k < items && i0 + k < ntiles) ? cnt[i0 + k] : 0u;
+        sum += v[k];
+    }
+    uint32_t inc = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = __shfl_up(inc, o, 64);
+        if (lane >= (uint32_t)o) inc += u;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    uint32_t run = inc - sum;
+#pragma unroll
+    for (uint32_t k = 0; k < 16; k++) run += k < w ? wsum[k] : 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < 16; k++) {
+        if (k < items && i0 + k < ntiles) {
+            const uint32_t end = run + v[k];
+            ranges[i0 + k] = (v[k] == 0u || end > cap) ? make_uint2(0u, 0u) : make_uint2(run, end);
+            cursor[i0 + k] = 0u;
+            run = end;
+        }
+    }
+}
+
+// ---- the per-tile sort
+// A tile's entries are ordered by the 64-bit key (depth bits << 32 | Gaussian).  The workgroup does not rank that key: it drops every
+// entry into one of CAP buckets by an order-preserving reduction of its depth bits, q = (bits - smallest bits of the list) >> shift, with
+// the shift that brings the list's depth range down to log2(CAP) bits -- one LDS atomic per entry for the bucket sizes, a scan of the
+// buckets, one more atomic per entry for its slot (about a fifth of the instructions of ballot-ranked radix passes over the 24 bits in
+// which a tile's depths differ, and instructions are what the kernel's time went to).  Entries of one bucket sit next to each other in
+// arrival order; tile_sort_emit then places every entry of such a run by counting the run's smaller 64-bit keys (a list of 800 in 2 048
+// buckets: runs of one to three).  Exact for any input; a list whose depths crowd into a few buckets pays run length squared.
+//
+// LDS of one sorting workgroup: up to CAP entries and CAP buckets.  Two instances: TILE_SORT_LDS entries (48 KB: three workgroups per CU)
+// is the longest list sorted in LDS; the tiles with up to TILE_SORT_SMALL entries -- at the BASELINE shapes nearly all: the longest lists
+// measured are 1 615 (config 4), 729 (shell scene), 3 287 (config 5) -- are sorted by a launch of the small instance (24 KB: six
+// workgroups per CU), the others by a second launch of the large one.
+constexpr int TILE_SORT_LDS = 4096;
+#ifndef FDGS_TILE_SORT_SMALL
+#define FDGS_TILE_SORT_SMALL 2048
+#endif
+constexpr int TILE_SORT_SMALL = FDGS_TILE_SORT_SMALL;
+template <int CAP>
+struct TileSortLds {
+    uint32_t key[CAP], val[CAP], bucket[CAP];
+    uint32_t wtmp[4], red[2][4];
+};
+struct TileSortQ { uint32_t kmin, shift; };      // q = (key - kmin) >> shift < CAP
+
+// S.key / S.val [0, n) <- the depth bits and Gaussians of the n entries gv[], ordered by q; returns the list's reduction to q
+template <int CAP>
+__device__ __forceinline__ TileSortQ tile_sort_lds(TileSortLds<CAP>& S, const uint32_t* __restrict__ depth_bits, const uint32_t* gv, uint32_t n) {
+    constexpr int ITEMS = CAP / 256;
+    constexpr uint32_t QBITS = CAP == 4096 ? 12u : CAP == 2048 ? 11u : 10u;
+    static_assert(CAP == (1 << QBITS), "one bucket per value of q");
+    const uint32_t t = threadIdx.x;
+    uint32_t key[ITEMS], val[ITEMS];
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+#pragma unroll
+    for (int j = 0; j < ITEMS; j++) {
+        const uint32_t i = j * 256u + t;
+        S.bucket[i] = 0u;
+        if (i < n) {
+            val[j] = gv[i]; key[j] = depth_bits[val[j]];
+            lo = key[j] < lo ? key[j] : lo; hi = key[j] > hi ? key[j] : hi;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t l2 = __shfl_xor(lo, o, 64), h2 = __shfl_xor(hi, o, 64);
+        lo = l2 < lo ? l2 : lo; hi = h2 > hi ? h2 : hi;
+    }
+    if ((t & 63) == 0) { S.red[0][t >> 6] = lo; S.red[1][t >> 6] = hi; }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; k++) { lo = S.red[0][k] < lo ? S.red[0][k] : lo; hi = S.red[1][k] > hi ? S.red[1][k] : hi; }
+    TileSortQ Q;
+    Q.kmin = lo;
+    const uint32_t range = hi - lo, nb = range ? 32u - (uint32_t)__clz((int)range) : 0u;
+    Q.shift = nb > QBITS ? nb - QBITS : 0u;
+#pragma unroll
+    for (int j = 0; j < ITEMS; j++)
+        if (j * 256u + t < n) atomicAdd(&S.bucket[(key[j] - Q.kmin) >> Q.shift], 1u);
+    __syncthreads();
+    {   // bucket sizes -> bucket starts: thread t owns ITEMS consecutive buckets
+        uint32_t v[ITEMS], sum = 0;
+#pragma unroll
+        for (int k = 0; k < ITEMS; k++) { v[k] = S.bucket[t * ITEMS + k]; sum += v[k]; }
+        uint32_t tot;
+        uint32_t run = block_excl_scan_256(sum, S.wtmp, &tot);
+#pragma unroll
+        for (int k = 0; k < ITEMS; k++) { S.bucket[t * ITEMS + k] = run; run += v[k]; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < ITEMS; j++) {
+        if (j * 256u + t < n) {
+            const uint32_t pos = atomicAdd(&S.bucket[(key[j] - Q.kmin) >> Q.shift], 1u);
+            S.key[pos] = key[j]; S.val[pos] = val[j];
+        }
+    }
+    __syncthreads();
+    return Q;
+}
+
+// hands every entry of the q-sorted S to put(position, key, val): its own position, or -- in a run of equal q, which sits in arrival
+// order -- the run's start plus the number of smaller (key, val) in the run
+template <int CAP, typename F>
+__device__ __forceinline__ void tile_sort_emit(const TileSortLds<CAP>& S, uint32_t n, const TileSortQ Q, F put) {
+    for (uint32_t i = threadIdx.x; i < n; i += 256) {
+        const uint32_t k = S.key[i], g = S.val[i], q = (k - Q.kmin) >> Q.shift;
+        uint32_t pos = i;
+        if ((i > 0 && ((S.key[i - 1] - Q.kmin) >> Q.shift) == q) || (i + 1 < n && ((S.key[i + 1] - Q.kmin) >> Q.shift) == q)) {
+            uint32_t s = i;
+            while (s > 0 && ((S.key[s - 1] - Q.kmin) >> Q.shift) == q) s--;
+            pos = s;
+            for (uint32_t m = s; m < n; m++) {
+                const uint32_t km = S.key[m];
+                if (((km - Q.kmin) >> Q.shift) != q) break;
+                pos += (km < k || (km == k && S.val[m] < g)) ? 1u : 0u;
+            }
+        }
+        put(pos, k, g);
+    }
+}
+
+// One workgroup per tile: sorts the tile's range of entries (tile_pairs_kernel<true> left their Gaussians in `ugid`) and writes pair_gid /
+// pair_tile.  Lists of up to `cap` (<= CAP) entries: one sort in LDS.  Longer lists (slow, exact): chunks of `cap` entries are sorted in LDS
+// and written back as (depth bits, Gaussian), then merged pairwise -- every entry finds its place in the merged run by a binary search in
+// the other run (the 64-bit keys are unique) -- ping-ponging between the idle halves of the binning buffer (`ukey`, `ugid`) and the output
+// halves of the same range.  This launch takes the tiles with more than `above` and at most `upto` entries.
+template <int CAP>
+__global__ void __launch_bounds__(256) tile_sort_kernel(const uint2* __restrict__ ranges, const uint32_t* __restrict__ depth_bits, uint32_t* ukey,
+                                                        uint32_t* ugid, uint32_t* out_tile, uint32_t* out_gid, uint32_t cap, uint32_t above,
+                                                        uint32_t upto) {
+    __shared__ TileSortLds<CAP> S;
+    const uint32_t tile = blockIdx.x, t = threadIdx.x;
+    const uint2 r = ranges[tile];
+    const uint32_t n = r.y - r.x;
+    if (n <= above || n > upto) return;
+    ukey += r.x; ugid += r.x; out_tile += r.x; out_gid += r.x;
+    if (n <= cap) {
+        const TileSortQ Q = tile_sort_lds(S, depth_bits, ugid, n);
+        tile_sort_emit(S, n, Q, [&](uint32_t pos, uint32_t, uint32_t g) { out_gid[pos] = g; out_tile[pos] = tile; });
+        return;
+    }
+    for (uint32_t c0 = 0; c0 < n; c0 += cap) {
+        const uint32_t m = n - c0 < cap ? n - c0 : cap;
+        const TileSortQ Q = tile_sort_lds(S, depth_bits, ugid + c0, m);
+        tile_sort_emit(S, m, Q, [&](uint32_t pos, uint32_t k, uint32_t g) { ukey[c0 + pos] = k; ugid[c0 + pos] = g; });
+        __syncthreads();
+    }
+    uint32_t *sk = ukey, *sg = ugid, *dk = out_tile, *dg = out_gid;
+    for (unsigned long long w = cap; w < n; w <<= 1) {
+        __threadfence_block();
+        __syncthreads();
+        for (uint32_t i = t; i < n; i += 256) {
+            const uint32_t a0 = (uint32_t)((i / (2 * w)) * (2 * w));
+            const uint32_t b0 = (unsigned long long)a0 + w < n ? (uint32_t)(a0 + w) : n;
+            const uint32_t e = (unsigned long long)a0 + 2 * w < n ? (uint32_t)(a0 + 2 * w) : n;
+            const unsigned long long key = ((unsigned long long)sk[i] << 32) | sg[i];
+            // entries of the other run in front of this one (unique keys: lower bound on either side)
+            uint32_t lo = i < b0 ? b0 : a0, hi = i < b0 ? e : b0;
+            const uint32_t first = lo;
+            while (lo < hi) {
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                const unsigned long long km = ((unsigned long long)sk[mid] << 32) | sg[mid];
+                if (km < key) lo = mid + 1; else hi = mid;
+            }
+            const uint32_t pos = a0 + (i < b0 ? i - a0 : i - b0) + (lo - first);
+            dk[pos] = (uint32_t)(key >> 32); dg[pos] = (uint32_t)key;
+        }
+        uint32_t* x = sk; sk = dk; dk = x;
+        x = sg; sg = dg; dg = x;
+    }
+    __threadfence_block();
+    __syncthreads();
+    for (uint32_t i = t; i < n; i += 256) {
+        if (sg != out_gid) out_gid[i] = sg[i];
+        out_tile[i] = tile;
+    }
+}
+
+// largest tile count form 1 runs at: its per-tile counters are privatised in LDS (64 KB at 16 384 tiles, 2048 x 2048 pixels); larger
+// images keep form 0
+constexpr int TILE_FORM1_MAX_TILES = 16384;
+// the binning form of an image: knob bin_form, 1 only where it has an instance; the default (-1) picks by shape -- form 1 wherever it
+// runs: it measured faster on every BASELINE shape and scene (profiles/tile_sort_ab.txt), no shape keeps form 0 by measurement
+static int bin_form_for(const ImgLayout& il) {
+    const int ntiles = il.gx * il.gy;
+    if (ntiles > TILE_FORM1_MAX_TILES || g_tune.bin_form == 0) return 0;
+    return 1;
+}
+
 }  // namespace fdgs
 
 using namespace fdgs;
@@ -437,6 +754,14 @@ static int bin_prepare_impl(void* stream_, const fdgs_raster_params* p, void* ge
     if (wait && !ev) FDGS_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     if (!skip_copy) FDGS_HIP_CHECK(hipMemcpyAsync(num_rendered_host, at<uint32_t>(geom, gl.total), 4, hipMemcpyDeviceToHost, stream));
     if (wait) FDGS_HIP_CHECK(hipEventRecord(ev, stream));
+    if (bin_form_for(img_layout(p->W, p->H)) == 1) {
+        // form 1 has no per-Gaussian stage: the count's read-back is all there is to prepare
+        if (wait) {
+            hipError_t e = hipEventSynchronize(ev);
+            if (e != hipSuccess) return fail(FDGS_E_HIP, "%s failed: %s", "hipEventSynchronize", hipGetErrorString(e));
+        }
+        return FDGS_OK;
+    }
     int in = 0;
     rc = radix_sort_pairs(stream, at<uint32_t>(geom, gl.keys0), at<uint32_t>(geom, gl.ids0), at<uint32_t>(geom, gl.keys1),
                           at<uint32_t>(geom, gl.ids1), (uint32_t)p->P, 32, at<uint32_t>(geom, gl.hist), gl.sort_blocks, p->debug,
@@ -485,6 +810,51 @@ static int bin_sort_impl(void* stream_, const fdgs_raster_params* p, void* geom,
     GeomLayout gl = geom_layout(p->P);
     BinLayout bl = bin_layout(R);
     const uint32_t* n_dev = from_device ? at<uint32_t>(geom, gl.total) : nullptr;
+    if (bin_form_for(il) == 1) {
+        // count -> scan (= ranges) -> emit -> per-tile sort.  The tiles' counters and cursors live in the image buffer's `todo` and `order_f`
+        // sections, which the blending pass fills only after this stage.  Capacity mode needs no device-side pair count: the scan drops
+        // the tiles that do not fit, the other kernels follow the ranges.
+        const uint32_t ntiles = (uint32_t)(il.gx * il.gy);
+        uint32_t* counts = at<uint32_t>(img, il.todo);
+        uint32_t* cursor = at<uint32_t>(img, il.order_f);
+        uint2* ranges = at<uint2>(img, il.ranges);
+        // the idle halves of the binning buffer: `ugid` takes the unsorted Gaussians of every range, `ukey` is merge space of lists too long for LDS
+        uint32_t *ukey = at<uint32_t>(binning, bl.tile1), *ugid = at<uint32_t>(binning, bl.gid1);
+        FDGS_REQUIRE(R < TP_DROPPED, "binning form 1 addresses fewer than 2^31 pairs");
+        const size_t lds = (size_t)ntiles * 4;
+        // Gaussians per workgroup: 256 while seven workgroups' counters fit a CU's LDS (many small workgroups balance better), else 1024, which
+        // keeps the CU's waves resident next to 64 KB of counters and spreads the two sweeps over the counters over four times the Gaussians
+        const int pair_threads = ntiles <= 5632 ? 256 : 1024;
+        static bool raised[FDGS_MAX_DEVICES] = {};
+        bool& up = raised[current_device_slot()];
+        if (!up) {
+            FDGS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tile_pairs_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, TILE_FORM1_MAX_TILES * 4));
+            FDGS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tile_pairs_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, TILE_FORM1_MAX_TILES * 4));
+            up = true;
+        }
+        FDGS_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)ntiles * 4, stream));
+        { FDGS_TIMED("tile_count", stream); hipLaunchKernelGGL(tile_pairs_kernel<false>, dim3(cdiv(p->P, pair_threads)), dim3(pair_threads), lds, stream, p->P, at<uint32_t>(geom, gl.tiles),
+                           at<uint2>(geom, gl.rect), at<uint4>(geom, gl.cullmask), at<uint32_t>(geom, gl.total), il.gx, ntiles,
+                           counts, ranges, ugid); }
+        FDGS_LAUNCH_CHECK("tile_count", p->debug, stream);
+        { FDGS_TIMED("tile_scan", stream); hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, stream, counts, ntiles, ranges, cursor, from_device ? R : 0xFFFFFFFFu); }
+        FDGS_LAUNCH_CHECK("tile_scan", p->debug, stream);
+        { FDGS_TIMED("tile_emit", stream); hipLaunchKernelGGL(tile_pairs_kernel<true>, dim3(cdiv(p->P, pair_threads)), dim3(pair_threads), lds, stream, p->P, at<uint32_t>(geom, gl.tiles),
+                           at<uint2>(geom, gl.rect), at<uint4>(geom, gl.cullmask), at<uint32_t>(geom, gl.total), il.gx, ntiles,
+                           cursor, ranges, ugid); }
+        FDGS_LAUNCH_CHECK("tile_emit", p->debug, stream);
+        const uint32_t sort_cap = g_tune.tile_sort_cap > 0 && g_tune.tile_sort_cap < TILE_SORT_LDS ? (uint32_t)g_tune.tile_sort_cap : (uint32_t)TILE_SORT_LDS;
+        const uint32_t small = sort_cap < (uint32_t)TILE_SORT_SMALL ? sort_cap : (uint32_t)TILE_SORT_SMALL;
+        {
+            FDGS_TIMED("tile_sort", stream);
+            hipLaunchKernelGGL(tile_sort_kernel<TILE_SORT_SMALL>, dim3(ntiles), dim3(256), 0, stream, ranges, at<uint32_t>(geom, gl.depth), ukey, ugid, at<uint32_t>(binning, bl.tile0),
+                               at<uint32_t>(binning, bl.gid0), small, 0u, small);
+            hipLaunchKernelGGL(tile_sort_kernel<TILE_SORT_LDS>, dim3(ntiles), dim3(256), 0, stream, ranges, at<uint32_t>(geom, gl.depth), ukey, ugid, at<uint32_t>(binning, bl.tile0),
+                               at<uint32_t>(binning, bl.gid0), sort_cap, small, 0xFFFFFFFFu);
+        }
+        FDGS_LAUNCH_CHECK("tile_sort", p->debug, stream);
+        return FDGS_OK;
+    }
     { FDGS_TIMED("expand_pairs", stream); hipLaunchKernelGGL(expand_pairs_kernel, dim3(cdiv(p->P, 256), 2), dim3(256), 0, stream, p->P, at<uint32_t>(geom, gl.ids0),
                        at<uint32_t>(geom, gl.offsets), at<uint32_t>(geom, gl.tiles), at<uint2>(geom, gl.rect), at<uint4>(geom, gl.cullmask),
                        at<uint32_t>(geom, gl.total), il.gx,

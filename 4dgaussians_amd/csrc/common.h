@@ -65,6 +65,8 @@ struct Tuning {
     int tile_order;  // FDGS_TILE_ORDER  1 = the blending kernels take their tiles heaviest-first (per XCD), 0 = in image order
     int row_compact; // FDGS_ROW_COMPACT 1 = the deformation backward walks the non-zero ROWS (saved activations + ordered input), 0 = 32-row tiles
     int d2_form;     // FDGS_D2_FORM     0 (default: the weight-stationary backward-data kernel, deform_bwd_ws.h, where it applies) | 32 (the 32-row kernel everywhere)
+    int bin_form;    // FDGS_BIN_FORM    0 = depth sort + pair expansion + global tile sort | 1 = pairs placed per tile + one LDS sort per tile (images of up to 16 384 tiles, else 0) | -1 (default) = by shape (binning.hip: bin_form_for)
+    int tile_sort_cap; // FDGS_TILE_SORT_CAP  bin_form 1: list length above which a tile takes the chunk-and-merge path; 0 (default) = the compiled LDS capacity (4 096), lower values are for tests
 };
 extern Tuning g_tune;
 

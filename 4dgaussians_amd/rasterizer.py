@@ -60,8 +60,8 @@ class GaussianRasterizationSettings(NamedTuple):
 #   "exact"            the reference's shape: four C calls, the blocking read-back between stage 2 and 3 (FDGS_BINNING=exact).  Also the
 #                      first frame of every (size, count) pair in the other modes.
 #   "capacity"         OPT-IN, never waits: the count is looked at when a later frame starts; a frame whose count exceeded its capacity has
-#                      dropped its FARTHEST pairs -- forward and backward alike, so its gradient is the exact gradient of the image it
-#                      returned -- raises a RuntimeWarning and is counted in `capacity_overflows`.  For loops that prefer a host that runs
+#                      dropped pairs (binning form 1: its last tiles in image order, whole lists; form 0: its FARTHEST pairs) -- forward
+#                      and backward alike, so its gradient is the exact gradient of the image it returned -- raises a RuntimeWarning and is counted in `capacity_overflows`.  For loops that prefer a host that runs
 #                      a full frame ahead over the guarantee (the frame is then NOT the reference's).
 # State is per host thread (threading.local): one thread drives a stream, as include/fdgs.h requires.
 BINNING = os.environ.get("FDGS_BINNING", "auto")
@@ -106,7 +106,8 @@ def _note_count(c):
     if c.capacity is not None and c.R > c.capacity:
         capacity_overflows += 1
         warnings.warn(f"fdgs rasterizer (BINNING='capacity'): a frame listed {c.R} (tile, Gaussian) pairs but its binning buffer was sized for "
-                      f"{c.capacity}: the farthest {c.R - c.capacity} pairs of that frame were dropped; the capacity grows from the next frame on "
+                      f"{c.capacity}: at least {c.R - c.capacity} pairs of that frame were dropped (its last tiles in image order; with binning "
+                      "form 0 its farthest pairs); the capacity grows from the next frame on "
                       "(the default BINNING='auto' finishes such a frame exactly instead)", RuntimeWarning, stacklevel=3)
 
 

@@ -43,14 +43,17 @@ int fdgs_abi_version(void);
  * roofline measurement).  fdgs_timing_report synchronises the device and writes "kernel_name count total_ms" lines. */
 int fdgs_timing_enable(int on);
 int fdgs_timing_report(char* buf, size_t buflen, int reset);
-/* Development / test knobs (ABI 4; ten since ABI 5, eleven since round 6).  The library holds ONE table of integer knobs; it is filled from the environment variables
+/* Development / test knobs (ABI 4; ten since ABI 5, eleven since round 6, thirteen with bin_form and tile_sort_cap).  The library holds ONE table of integer knobs; it is filled from the environment variables
  * FDGS_<NAME> once, when the library is loaded, and afterwards changes only through fdgs_tuning_set -- no entry point reads the
  * environment.  Knobs select between equivalent kernel forms or launch shapes (same results up to summation order), never semantics:
  *   d1_form (0 | 8 | 16 | 32), d1_wgs, d1_split, skip_dead, d4_mfma, d4_rows_kb, tile_cull (0 = the reference's rectangle lists), rbwd_ppl (-1 = by image size | 4 | 2 | 0),
  *   tile_order (1 = the blending kernels take their tiles heaviest-first, 0 = image order), row_compact (1 = the deformation backward walks
  *   the non-zero rows instead of the non-zero 32-row tiles where it can; 2 = the same with the row lists built by the two-launch form),
  *   d2_form (0 = the weight-stationary backward-data kernel where it applies -- row lists, net_width 128, C*L 32 or 48, five heads or position + scale + rotation --, 32 = the
- *   32-row kernel everywhere).
+ *   32-row kernel everywhere),
+ *   bin_form (0 = depth sort of the Gaussians + pair expansion + global tile sort, 1 = pairs placed per tile + one LDS sort per tile --
+ *   images of up to 16 384 tiles, larger ones keep form 0 --, -1 = by shape; same lists bit for bit), tile_sort_cap (bin_form 1: list
+ *   length above which a tile's sort takes the chunk-and-merge path; 0 = the compiled LDS capacity, 4 096; lower values are for tests).
  * `name` is the lower- or upper-case knob name, with or without the FDGS_ prefix.  Process-global, not thread-safe against running calls:
  * set knobs between frames.  fdgs_tuning_reset restores the load-time values.  See INTEGRATION.md ("Knobs"). */
 int fdgs_tuning_set(const char* name, int value);
@@ -115,7 +118,10 @@ int fdgs_bin_sort(void* stream, const fdgs_raster_params* p, void* geom, void* b
  * work on min(true, capacity) pairs -- and reaches *num_rendered_host (pinned host memory) asynchronously (ABI 6: a store of the LAST
  * workgroup of the projection kernel when the word is device-visible -- hipHostGetDevicePointer --, i.e. while the depth sort is still
  * running; a copy node otherwise): pre-set the word to 0xFFFFFFFF and read it once it changed (fdgs_pair_count_wait).  true > capacity
- * means the FARTHEST pairs of this frame were dropped (pairs are emitted in depth order) and the image is NOT the reference's: the
+ * means that pairs of this frame were dropped and the image is NOT the reference's -- with binning form 1 (tuning knob bin_form) the
+ * frame keeps WHOLE TILES, in image order, while their lists fit: the first tile whose list would end behind `capacity` and every tile
+ * after it get the range (0, 0), and no kept list is truncated; with form 0 the FARTHEST pairs are dropped (pairs are emitted in depth
+ * order).  Either way nothing is written out of bounds and ranges[:, 1] <= capacity.  The
  * stage-1/2 results in `geom` are complete and valid, so the caller finishes the frame exactly with fdgs_bin_sort + fdgs_render_fwd on a
  * buffer of fdgs_binning_bytes(true) bytes (what the Python host does before it hands the image to anyone: the reference never truncates,
  * SURVEY Appendix B.2).  The buffers are laid out for `capacity`: pass `capacity` as num_rendered to fdgs_raster_bwd /
@@ -197,6 +203,8 @@ int fdgs_mark_visible(void* stream, int P, const float* means3D, const float* vi
  * 3 recC float4[P] (r,g,b,0); 4 cov3D f32[P,6]; 5 tiles_touched u32[P]; 6 clamped u32[P] (bit c = channel c);
  * 7 rect u32[P,2] (xmin|ymin<<16, xmax|ymax<<16); 8 sorted Gaussian ids u32[P]; 9 point_offsets u32[P] (inclusive, depth
  * order; ABI 5: LOCAL to chunks of 4096 Gaussians -- the pair expansion adds the totals of the chunks in front itself).
+ * Fields 8 and 9 are defined only for binning form 0 (tuning knob bin_form): form 1 has no depth sort of the Gaussians and does not
+ * produce them (field 8 then holds the identity the projection kernel wrote, field 9 is not written).
  *
  * Field 3 (recC) may be REWRITTEN between two fdgs_render_fwd calls of a FORWARD-ONLY frame: a frame queued with acc_zero == NULL that
  * no fdgs_raster_bwd will follow.  recC is the only thing the blend reads that depends on colour, the blend is linear in it and never
