@@ -20,6 +20,7 @@ const KnobDesc kKnobs[] = {
     {"D4_MFMA", &Tuning::d4_mfma, -1}, {"D4_ROWS_KB", &Tuning::d4_rows_kb, -1}, {"TILE_CULL", &Tuning::tile_cull, 1}, {"RBWD_PPL", &Tuning::rbwd_ppl, -1},
     {"TILE_ORDER", &Tuning::tile_order, 1}, {"ROW_COMPACT", &Tuning::row_compact, 1}, {"D2_FORM", &Tuning::d2_form, 0},
     {"BIN_FORM", &Tuning::bin_form, -1}, {"TILE_SORT_CAP", &Tuning::tile_sort_cap, 0},
+    {"BIN_COUNT", &Tuning::bin_count, 1}, {"BLEND_FWD_FORM", &Tuning::blend_fwd_form, 1},
 };
 Tuning tuning_from_environment() {       // runs once, from the static initialiser below (library load)
     Tuning t{};

@@ -18,6 +18,7 @@
 // instead of 21.  Form 0 stays: spatial.hip sorts with radix_sort_pairs, images of more than 16 384 tiles run it, and A/B legs need it.
 #include "common.h"
 #include "raster.h"
+#include "tile_walk.h"
 
 namespace fdgs {
 
@@ -407,56 +408,6 @@ __global__ void __launch_bounds__(256) tile_ranges_kernel(const uint32_t* __rest
 // arrival order, (4) tile_sort_kernel fetches the Gaussians' depths and orders each range by the 64-bit key (depth bits << 32 | Gaussian)
 // -- unique per pair, so the result does not depend on the arrival order and equals the order of the two stable sorts of form 0 (depth,
 // ties by index).
-//
-// The pairs of a Gaussian are the tiles of its square, under culling the set bits of its 256-bit mask (squares of more than 256 tiles are
-// not culled): the pair set of expand_pairs_kernel.  walk_pairs() hands every pair of a wave's 64 Gaussians to `f`: a square of up to 64
-// tiles is walked by its own lane (its mask is one 64-bit word: pop the lowest set bit), a larger one by the whole wave, 64 tiles per
-// round (the nearest Gaussians cover 60+ tiles each: one lane would keep 63 waiting).  Must be called by all lanes of the wave.
-template <typename F>
-__device__ __forceinline__ void walk_pairs(uint32_t cnt, uint2 rc, uint4 mlo, uint4 mhi, bool culled, uint32_t gx, uint32_t gid, F f) {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t xmin = rc.x & 0xFFFFu, ymin = rc.x >> 16, w = (rc.y & 0xFFFFu) - xmin, h = (rc.y >> 16) - ymin;
-    const uint32_t area = cnt ? w * h : 0u;
-    const bool masked = culled && area <= 256u;
-    if (area != 0u && area <= 64u) {
-        unsigned long long m = masked ? (((unsigned long long)mlo.y << 32) | mlo.x) : (area == 64u ? ~0ull : (1ull << area) - 1ull);
-        const uint32_t inv = (65536u + w - 1u) / w;          // l / w = (l * inv) >> 16 for l < 64, w <= 64
-        const uint32_t tile0 = ymin * gx + xmin;
-        while (m) {
-            const uint32_t l = (uint32_t)__ffsll((unsigned long long)m) - 1u;
-            m &= m - 1ull;
-            const uint32_t q = (l * inv) >> 16;
-            f(tile0 + q * gx + (l - q * w), gid);
-        }
-    }
-    uint64_t big = __ballot(area > 64u);
-    while (big) {
-        const int src = __ffsll((unsigned long long)big) - 1;
-        big &= big - 1ull;
-        const uint32_t brx = __shfl(rc.x, src, 64), bry = __shfl(rc.y, src, 64), bgid = __shfl(gid, src, 64);
-        const uint32_t bx = brx & 0xFFFFu, by = brx >> 16, bw = (bry & 0xFFFFu) - bx, barea = bw * ((bry >> 16) - by);
-        if (culled && barea <= 256u) {
-            // bit l of the mask = 32-bit word l / 32, bit l % 32: round k looks at l = 64 k + lane
-            const uint32_t w0 = __shfl(mlo.x, src, 64), w1 = __shfl(mlo.y, src, 64), w2 = __shfl(mlo.z, src, 64), w3 = __shfl(mlo.w, src, 64);
-            const uint32_t w4 = __shfl(mhi.x, src, 64), w5 = __shfl(mhi.y, src, 64), w6 = __shfl(mhi.z, src, 64), w7 = __shfl(mhi.w, src, 64);
-            const bool up = lane >= 32u;
-            const uint32_t word[4] = {up ? w1 : w0, up ? w3 : w2, up ? w5 : w4, up ? w7 : w6};
-#pragma unroll
-            for (uint32_t k = 0; k < 4; k++) {
-                const uint32_t l = 64u * k + lane;
-                if (l < barea && ((word[k] >> (lane & 31u)) & 1u)) {
-                    const uint32_t q = l / bw;
-                    f((by + q) * gx + bx + (l - q * bw), bgid);
-                }
-            }
-        } else {
-            for (uint32_t l = lane; l < barea; l += 64u) {
-                const uint32_t q = l / bw;
-                f((by + q) * gx + bx + (l - q * bw), bgid);
-            }
-        }
-    }
-}
 
 // A workgroup owns blockDim.x consecutive Gaussians and privatises the tiles' counters in LDS (ds_add; global atomics into a few hot cells
 // run at 5 G/s).  Count: walk, then ONE global atomic per touched tile onto the tile's counter.  Emit: the same walk, then one
@@ -468,7 +419,8 @@ template <bool EMIT>
 __global__ void __launch_bounds__(1024) tile_pairs_kernel(int P, const uint32_t* __restrict__ tiles, const uint2* __restrict__ rect,
                                                           const uint4* __restrict__ cullmask, const uint32_t* __restrict__ total, int gx,
                                                           uint32_t ntiles, uint32_t* __restrict__ gcount /* count: the tiles' counters; emit: their cursors */,
-                                                          const uint2* __restrict__ ranges, uint32_t* __restrict__ ugid) {
+                                                          const uint2* __restrict__ ranges, uint32_t* __restrict__ ugid,
+                                                          int on_counts /* emit: gcount still holds the tiles' COUNTS (the chain without a cursor) */) {
     extern __shared__ uint32_t s_cnt[];       // [ntiles]
     const bool culled = total[2] != 0;
     const uint32_t t = threadIdx.x, i = blockIdx.x * blockDim.x + t;
@@ -491,7 +443,8 @@ __global__ void __launch_bounds__(1024) tile_pairs_kernel(int P, const uint32_t*
         if (n) {
             if (EMIT) {
                 const uint2 r = ranges[k];     // (capacity mode: a tile whose list does not fit has the range (0, 0): its pairs are dropped)
-                s_cnt[k] = r.y ? r.x + atomicAdd(&gcount[k], n) : TP_DROPPED;
+                // (on_counts: no cursor was ever cleared -- the counter already holds the tile's count r.y - r.x and goes on counting from there)
+                s_cnt[k] = r.y ? r.x + atomicAdd(&gcount[k], n) - (on_counts ? r.y - r.x : 0u) : TP_DROPPED;
             } else {
                 atomicAdd(&gcount[k], n);
             }
@@ -506,41 +459,13 @@ __global__ void __launch_bounds__(1024) tile_pairs_kernel(int P, const uint32_t*
     }
 }
 
-// One workgroup: exclusive scan of the tiles' pair counts = the tiles' slot ranges, written as `ranges`; empty tiles get (0, 0).  `cap`
-// (capacity mode): a tile whose range would end behind it gets (0, 0) too, and so does every tile after it (the ends never decrease): the
-// frame keeps whole tiles, in image order, while they fit.  The cursors of tile_pairs_kernel<true> start at 0.
-// 1024 threads, up to 16 consecutive tiles each (ntiles <= TILE_FORM1_MAX_TILES = 16 384): one round of loads, one scan over the threads.
+// One workgroup: the scan of the tiles' pair counts into their slot ranges (tile_walk.h: tile_scan_body); the cursors of
+// tile_pairs_kernel<true> start at 0.  (The chain of a frame that counted in its projection runs the same scan in one grid with the forward's
+// tile order and keeps no cursor: render.hip, tile_scan_order_kernel.)
 __global__ void __launch_bounds__(1024) tile_scan_kernel(const uint32_t* __restrict__ cnt, uint32_t ntiles, uint2* __restrict__ ranges,
                                                          uint32_t* __restrict__ cursor, uint32_t cap) {
     __shared__ uint32_t wsum[16];
-    const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const uint32_t items = (ntiles + 1023u) >> 10, i0 = t * items;
-    uint32_t v[16], sum = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 16; k++) {
-        v[k] = (k < items && i0 + k < ntiles) ? cnt[i0 + k] : 0u;
-        sum += v[k];
-    }
-    uint32_t inc = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(inc, o, 64);
-        if (lane >= (uint32_t)o) inc += u;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    uint32_t run = inc - sum;
-#pragma unroll
-    for (uint32_t k = 0; k < 16; k++) run += k < w ? wsum[k] : 0u;
-#pragma unroll
-    for (uint32_t k = 0; k < 16; k++) {
-        if (k < items && i0 + k < ntiles) {
-            const uint32_t end = run + v[k];
-            ranges[i0 + k] = (v[k] == 0u || end > cap) ? make_uint2(0u, 0u) : make_uint2(run, end);
-            cursor[i0 + k] = 0u;
-            run = end;
-        }
-    }
+    tile_scan_body(wsum, cnt, ntiles, ranges, cursor, cap);
 }
 
 // ---- the per-tile sort
@@ -702,15 +627,17 @@ __global__ void __launch_bounds__(256) tile_sort_kernel(const uint2* __restrict_
     }
 }
 
-// largest tile count form 1 runs at: its per-tile counters are privatised in LDS (64 KB at 16 384 tiles, 2048 x 2048 pixels); larger
-// images keep form 0
-constexpr int TILE_FORM1_MAX_TILES = 16384;
+// (images of more than TILE_FORM1_MAX_TILES tiles, common.h, keep form 0)
 // the binning form of an image: knob bin_form, 1 only where it has an instance; the default (-1) picks by shape -- form 1 wherever it
 // runs: it measured faster on every BASELINE shape and scene (profiles/tile_sort_ab.txt), no shape keeps form 0 by measurement
 static int bin_form_for(const ImgLayout& il) {
     const int ntiles = il.gx * il.gy;
     if (ntiles > TILE_FORM1_MAX_TILES || g_tune.bin_form == 0) return 0;
     return 1;
+}
+bool counts_in_projection(const ImgLayout& il) {
+    if (bin_form_for(il) != 1) return false;
+    return g_tune.bin_count == 2 || (g_tune.bin_count == 1 && il.gx * il.gy <= FUSED_COUNT_MAX_TILES);
 }
 
 }  // namespace fdgs
@@ -796,8 +723,10 @@ extern "C" int fdgs_bin_prepare(void* stream_, const fdgs_raster_params* p, void
 
 // pair expansion + tile sort + ranges.  from_device: R is the CAPACITY of `binning`; the kernels read the true pair count from the geom
 // buffer and work on min(true, capacity) pairs
+// counted (one-call frame): the projection left the tiles' pair counts in geom (counts_in_projection); *order_made: the forward's tile order
+// was written on the way
 static int bin_sort_impl(void* stream_, const fdgs_raster_params* p, void* geom, void* binning, void* img, uint32_t R, bool from_device,
-                         uint32_t* host_count_dev = nullptr) {
+                         uint32_t* host_count_dev = nullptr, bool counted = false, bool* order_made = nullptr) {
     int rc = validate_raster_params(p);
     if (rc) return rc;
     FDGS_REQUIRE(geom && img && (binning || R == 0), "geom/binning/img is NULL");
@@ -814,8 +743,11 @@ static int bin_sort_impl(void* stream_, const fdgs_raster_params* p, void* geom,
         // count -> scan (= ranges) -> emit -> per-tile sort.  The tiles' counters and cursors live in the image buffer's `todo` and `order_f`
         // sections, which the blending pass fills only after this stage.  Capacity mode needs no device-side pair count: the scan drops
         // the tiles that do not fit, the other kernels follow the ranges.
+        // `counted`: the projection kernel has counted already, into geom's tile_counts; the scan shares a launch with the forward's tile
+        // order (which therefore takes `order_f`), and the emit claims its slots on the counters themselves: no count launch, no fill, no
+        // cursor.  The staged calls and the exact rerun of an overflowed frame come here with counted = false, on a geom of either projection.
         const uint32_t ntiles = (uint32_t)(il.gx * il.gy);
-        uint32_t* counts = at<uint32_t>(img, il.todo);
+        uint32_t* counts = counted ? at<uint32_t>(geom, gl.tile_counts) : at<uint32_t>(img, il.todo);
         uint32_t* cursor = at<uint32_t>(img, il.order_f);
         uint2* ranges = at<uint2>(img, il.ranges);
         // the idle halves of the binning buffer: `ugid` takes the unsorted Gaussians of every range, `ukey` is merge space of lists too long for LDS
@@ -832,16 +764,21 @@ static int bin_sort_impl(void* stream_, const fdgs_raster_params* p, void* geom,
             FDGS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tile_pairs_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, TILE_FORM1_MAX_TILES * 4));
             up = true;
         }
-        FDGS_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)ntiles * 4, stream));
-        { FDGS_TIMED("tile_count", stream); hipLaunchKernelGGL(tile_pairs_kernel<false>, dim3(cdiv(p->P, pair_threads)), dim3(pair_threads), lds, stream, p->P, at<uint32_t>(geom, gl.tiles),
-                           at<uint2>(geom, gl.rect), at<uint4>(geom, gl.cullmask), at<uint32_t>(geom, gl.total), il.gx, ntiles,
-                           counts, ranges, ugid); }
-        FDGS_LAUNCH_CHECK("tile_count", p->debug, stream);
-        { FDGS_TIMED("tile_scan", stream); hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, stream, counts, ntiles, ranges, cursor, from_device ? R : 0xFFFFFFFFu); }
-        FDGS_LAUNCH_CHECK("tile_scan", p->debug, stream);
+        if (counted) {
+            rc = launch_tile_scan_order(stream, il, counts, img, from_device ? R : 0xFFFFFFFFu, p->debug, order_made);
+            if (rc) return rc;
+        } else {
+            FDGS_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)ntiles * 4, stream));
+            { FDGS_TIMED("tile_count", stream); hipLaunchKernelGGL(tile_pairs_kernel<false>, dim3(cdiv(p->P, pair_threads)), dim3(pair_threads), lds, stream, p->P, at<uint32_t>(geom, gl.tiles),
+                               at<uint2>(geom, gl.rect), at<uint4>(geom, gl.cullmask), at<uint32_t>(geom, gl.total), il.gx, ntiles,
+                               counts, ranges, ugid, 0); }
+            FDGS_LAUNCH_CHECK("tile_count", p->debug, stream);
+            { FDGS_TIMED("tile_scan", stream); hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, stream, counts, ntiles, ranges, cursor, from_device ? R : 0xFFFFFFFFu); }
+            FDGS_LAUNCH_CHECK("tile_scan", p->debug, stream);
+        }
         { FDGS_TIMED("tile_emit", stream); hipLaunchKernelGGL(tile_pairs_kernel<true>, dim3(cdiv(p->P, pair_threads)), dim3(pair_threads), lds, stream, p->P, at<uint32_t>(geom, gl.tiles),
                            at<uint2>(geom, gl.rect), at<uint4>(geom, gl.cullmask), at<uint32_t>(geom, gl.total), il.gx, ntiles,
-                           cursor, ranges, ugid); }
+                           counted ? counts : cursor, ranges, ugid, counted ? 1 : 0); }
         FDGS_LAUNCH_CHECK("tile_emit", p->debug, stream);
         const uint32_t sort_cap = g_tune.tile_sort_cap > 0 && g_tune.tile_sort_cap < TILE_SORT_LDS ? (uint32_t)g_tune.tile_sort_cap : (uint32_t)TILE_SORT_LDS;
         const uint32_t small = sort_cap < (uint32_t)TILE_SORT_SMALL ? sort_cap : (uint32_t)TILE_SORT_SMALL;
@@ -891,13 +828,15 @@ extern "C" int fdgs_raster_fwd_capacity(void* stream, const fdgs_raster_params* 
     void* dp = nullptr;
     const bool zero_copy = p && p->P > 0 && hipHostGetDevicePointer(&dp, num_rendered_host, 0) == hipSuccess && dp != nullptr;
     if (!zero_copy) (void)hipGetLastError();
-    int rc = fdgs_preprocess_fwd_impl(stream, p, geom, radii, zero_copy ? reinterpret_cast<uint32_t*>(dp) : nullptr);
+    const bool counted = p && p->P > 0 && p->W > 0 && p->H > 0 && counts_in_projection(img_layout(p->W, p->H));
+    int rc = fdgs_preprocess_fwd_impl(stream, p, geom, radii, zero_copy ? reinterpret_cast<uint32_t*>(dp) : nullptr, counted);
     if (rc) return rc;
     rc = bin_prepare_impl(stream, p, geom, num_rendered_host, false, zero_copy);
     if (rc) return rc;
-    rc = bin_sort_impl(stream, p, geom, binning, img, capacity, true, nullptr);
+    bool order_made = false;
+    rc = bin_sort_impl(stream, p, geom, binning, img, capacity, true, nullptr, counted, &order_made);
     if (rc) return rc;
-    return fdgs_render_fwd(stream, p, geom, binning, img, capacity, out_color, out_depth);
+    return render_fwd_impl(stream, p, geom, binning, img, capacity, out_color, out_depth, order_made);
 }
 
 // Host side of the verified capacity path: wait until the pair count of a frame queued by fdgs_raster_fwd_capacity has reached its pinned

@@ -67,6 +67,8 @@ struct Tuning {
     int d2_form;     // FDGS_D2_FORM     0 (default: the weight-stationary backward-data kernel, deform_bwd_ws.h, where it applies) | 32 (the 32-row kernel everywhere)
     int bin_form;    // FDGS_BIN_FORM    0 = depth sort + pair expansion + global tile sort | 1 = pairs placed per tile + one LDS sort per tile (images of up to 16 384 tiles, else 0) | -1 (default) = by shape (binning.hip: bin_form_for)
     int tile_sort_cap; // FDGS_TILE_SORT_CAP  bin_form 1: list length above which a tile takes the chunk-and-merge path; 0 (default) = the compiled LDS capacity (4 096), lower values are for tests
+    int bin_count;   // FDGS_BIN_COUNT   bin_form 1, one-call frame (fdgs_raster_fwd_capacity): 0 = a count launch of its own, then scan, emit on cleared cursors, tile order | 1 = the projection kernel counts (images of up to FUSED_COUNT_MAX_TILES tiles), scan and forward tile order in one launch, emit on the counters | 2 = as 1 at every tile count form 1 runs at (measurements)
+    int blend_fwd_form; // FDGS_BLEND_FWD_FORM  inner loop of render_fwd_kernel: 0 = one list entry per trip | 1 = two per trip, packed across the entries
 };
 extern Tuning g_tune;
 
@@ -127,8 +129,14 @@ constexpr int RADIX_BITS = 8;
 constexpr int RADIX = 1 << RADIX_BITS;
 
 // ---- geom buffer layout (struct of arrays, 256-B aligned sections) ----
+// largest tile count binning form 1 runs at: its per-tile counters are privatised in LDS (64 KB at 16 384 tiles, 2048 x 2048 pixels)
+constexpr int TILE_FORM1_MAX_TILES = 16384;
+// largest tile count at which the projection kernel counts the tiles' pairs itself (knob bin_count = 1): its workgroups have 256 threads, and
+// up to here seven of them keep their counters in a CU's LDS next to each other -- the bound at which the count kernel of binning.hip
+// switches to 1 024 threads for the same reason
+constexpr int FUSED_COUNT_MAX_TILES = 5632;
 struct GeomLayout {
-    size_t depth, recA, recB, recC, cov3D, tiles, clamped, rect, keys0, keys1, ids0, ids1, offsets, hist, total, cullmask, bytes;
+    size_t depth, recA, recB, recC, cov3D, tiles, clamped, rect, keys0, keys1, ids0, ids1, offsets, hist, total, tile_counts, cullmask, bytes;
     int sort_blocks;
 };
 inline GeomLayout geom_layout(int P) {
@@ -137,6 +145,7 @@ inline GeomLayout geom_layout(int P) {
     size_t n = (size_t)(P > 0 ? P : 1);
     auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes); return r; };
     g.total = take(256);  // [0] = total tiles touched (u32), [1] = scan carry scratch, [2] = 1 when tiles were culled
+    g.tile_counts = take((size_t)TILE_FORM1_MAX_TILES * 4);   // the tiles' pair counters of a projection that counts: directly behind `total`, ONE fill clears both
     g.depth = take(n * 4);
     g.recA = take(n * 16);
     g.recB = take(n * 16);

@@ -6,6 +6,7 @@
 #include "common.h"
 #include "gs_math.h"
 #include "raster.h"
+#include "tile_walk.h"
 
 namespace fdgs {
 
@@ -42,6 +43,7 @@ struct PreFwdArgs : FrameHead {
     int32_t* radii;
     uint8_t* visibility;         // opt: radii > 0
     int cull; uint4* cullmask;   // exact tile culling (gs_math.h): 256-bit tile mask per Gaussian, two uint4 each
+    uint32_t* tile_counts; uint32_t ntiles;      // opt (one-call frame, knob bin_count): the tiles' pair counters, zero at the start, counted here
 };
 
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
@@ -50,11 +52,16 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
     return v;
 }
 
+// COUNT: the kernel also counts the pairs of every tile (a.tile_counts; the one-call frame with knob bin_count).  An instantiation of its own:
+// the staged calls and the images that keep the count launch run the kernel without the square and the mask held to its end.
+template <bool COUNT>
 __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreFwdArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     CamConst c;
     load_cam(c, a.view, a.proj, a.campos, a.W, a.H, a.tanfovx, a.tanfovy, a.scale_mod, a.D, a.M);
     uint32_t my_tiles = 0;
+    uint2 my_rect = make_uint2(0u, 0u);                                  // what the per-tile count at the end walks: the square ...
+    unsigned long long my_mask[4] = {0ull, 0ull, 0ull, 0ull};           // ... and, culled, the tiles of it that can receive a contribution
     if (i < a.P) {
         float p[3] = {a.means3D[3 * (size_t)i], a.means3D[3 * (size_t)i + 1], a.means3D[3 * (size_t)i + 2]};
         float c6[6];
@@ -99,7 +106,8 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreFwdArgs a) {
 #pragma unroll
             for (int k = 0; k < 6; k++) a.cov3D[6 * (size_t)i + k] = c6[k];
             a.clamped[i] = cl;
-            a.rect[i] = make_uint2(g.rect_min, g.rect_max);
+            my_rect = make_uint2(g.rect_min, g.rect_max);
+            a.rect[i] = my_rect;
             radius = g.radius;
             my_tiles = (uint32_t)g.tiles;
             if (a.cull && g.tiles <= 256) {
@@ -128,6 +136,8 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreFwdArgs a) {
                     }
                 }
                 my_tiles = cnt;
+#pragma unroll
+                for (int q = 0; q < 4; q++) my_mask[q] = m[q];
                 a.cullmask[2 * (size_t)i] = make_uint4((uint32_t)m[0], (uint32_t)(m[0] >> 32), (uint32_t)m[1], (uint32_t)(m[1] >> 32));
                 a.cullmask[2 * (size_t)i + 1] = make_uint4((uint32_t)m[2], (uint32_t)(m[2] >> 32), (uint32_t)m[3], (uint32_t)(m[3] >> 32));
             }
@@ -158,6 +168,15 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreFwdArgs a) {
         }
     }
     if (i == 0) a.total[2] = a.cull ? 1u : 0u;   // the pair expansion reads which list semantics the counts have
+    // The tiles' pair counts, while the count, the square and the mask are still in registers (what tile_pairs_kernel<false> of binning.hip
+    // would load again): the kernel's last act, behind the ticket above, so the pair count reaches the host no later than it did.  Every
+    // thread of the workgroup arrives here (nothing above returns), nothing diverges.
+    if constexpr (COUNT) {
+        extern __shared__ uint32_t s_cnt[];       // [ntiles]
+        count_tile_pairs(s_cnt, my_tiles, my_rect, make_uint4((uint32_t)my_mask[0], (uint32_t)(my_mask[0] >> 32), (uint32_t)my_mask[1], (uint32_t)(my_mask[1] >> 32)),
+                         make_uint4((uint32_t)my_mask[2], (uint32_t)(my_mask[2] >> 32), (uint32_t)my_mask[3], (uint32_t)(my_mask[3] >> 32)), a.cull != 0,
+                         (uint32_t)c.gx, a.ntiles, a.tile_counts);
+    }
 }
 
 struct PreBwdArgs : FrameHead {
@@ -488,13 +507,17 @@ int validate_raster_params(const fdgs_raster_params* p) {
 
 using namespace fdgs;
 
-int fdgs_preprocess_fwd_impl(void* stream_, const fdgs_raster_params* p, void* geom, int32_t* radii, uint32_t* host_count_dev) {
+int fdgs_preprocess_fwd_impl(void* stream_, const fdgs_raster_params* p, void* geom, int32_t* radii, uint32_t* host_count_dev, bool count_tiles) {
     int rc = validate_raster_params(p);
     if (rc) return rc;
     FDGS_REQUIRE(geom && (radii || p->P == 0), "geom/radii is NULL");
     hipStream_t stream = (hipStream_t)stream_;
     GeomLayout gl = geom_layout(p->P);
-    FDGS_HIP_CHECK(hipMemsetAsync(at<char>(geom, gl.total), 0, 256, stream));
+    const uint32_t ntiles = (uint32_t)(((p->W + TILE - 1) / TILE) * ((p->H + TILE - 1) / TILE));
+    count_tiles = count_tiles && p->P > 0;
+    FDGS_REQUIRE(!count_tiles || ntiles <= (uint32_t)TILE_FORM1_MAX_TILES, "too many tiles to count in the projection");
+    // (the tile counters sit directly behind the header: one fill clears both)
+    FDGS_HIP_CHECK(hipMemsetAsync(at<char>(geom, gl.total), 0, 256 + (count_tiles ? (size_t)ntiles * 4 : 0), stream));
     if (p->P == 0) return FDGS_OK;
     PreFwdArgs a{};
     fill_frame_head(a, p);
@@ -506,7 +529,19 @@ int fdgs_preprocess_fwd_impl(void* stream_, const fdgs_raster_params* p, void* g
     a.ids = at<uint32_t>(geom, gl.ids0); a.total = at<uint32_t>(geom, gl.total); a.radii = radii; a.visibility = p->visibility;
     a.cull = g_tune.tile_cull != 0; a.cullmask = at<uint4>(geom, gl.cullmask);
     a.host_count = host_count_dev;
-    { FDGS_TIMED("preprocess_fwd", stream); hipLaunchKernelGGL(preprocess_fwd_kernel, dim3(cdiv(p->P, 256)), dim3(256), 0, stream, a); }
+    size_t lds = 0;
+    if (count_tiles) {
+        FDGS_REQUIRE(gl.tile_counts == gl.total + 256, "the tile counters follow the header");
+        a.tile_counts = at<uint32_t>(geom, gl.tile_counts); a.ntiles = ntiles;
+        lds = (size_t)ntiles * 4;
+        static bool raised[FDGS_MAX_DEVICES] = {};
+        bool& up = raised[current_device_slot()];
+        if (!up) {
+            FDGS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, TILE_FORM1_MAX_TILES * 4));
+            up = true;
+        }
+    }
+    { FDGS_TIMED("preprocess_fwd", stream); hipLaunchKernelGGL(count_tiles ? preprocess_fwd_kernel<true> : preprocess_fwd_kernel<false>, dim3(cdiv(p->P, 256)), dim3(256), lds, stream, a); }
     FDGS_LAUNCH_CHECK("preprocess_fwd", p->debug, stream);
     return FDGS_OK;
 }

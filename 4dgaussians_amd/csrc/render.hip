@@ -16,6 +16,7 @@
 #include "common.h"
 #include "gs_math.h"
 #include "raster.h"
+#include "tile_walk.h"
 
 namespace fdgs {
 
@@ -52,10 +53,11 @@ __device__ __forceinline__ int unit_lookup(const uint32_t* __restrict__ order, i
 // One 1024-thread workgroup per XCD: counting sort of the XCD's tiles by descending key (256 levels of the XCD's largest key; LPT needs
 // no finer order), key = list length (mode 0, forward) or the forward's per-tile `todo` (mode 1, backward).  Padding slots of the map
 // (rows below the image) and tiles with key 0 go last.
-__global__ void __launch_bounds__(1024) tile_order_kernel(int mode, int gx, int gy, int bh, int per_xcd, const uint2* __restrict__ ranges,
-                                                          const uint32_t* __restrict__ todo, uint32_t* __restrict__ order) {
-    __shared__ uint32_t hist[256], base[256], smax;
-    const int x = blockIdx.x, t = threadIdx.x;
+// (the body: XCD x's list from key_of(tile), by the 1024 threads of one workgroup; hist, base [256] and smax in LDS)
+template <typename KeyF>
+__device__ __forceinline__ void tile_order_body(uint32_t* hist, uint32_t* base, uint32_t& smax, int x, int gx, int gy, int bh, int per_xcd,
+                                                uint32_t* __restrict__ order, KeyF key_of) {
+    const int t = threadIdx.x;
     if (t < 256) hist[t] = 0;
     if (t == 0) smax = 0;
     __syncthreads();
@@ -68,7 +70,7 @@ __global__ void __launch_bounds__(1024) tile_order_kernel(int mode, int gx, int 
         const int idx = t + 1024 * i;
         tile[i] = idx < per_xcd ? unit_of_block(idx * 8 + x, gx, gy, 1, bh) : -2;      // -1: padding slot of the map, -2: beyond the map
         key[i] = 0;
-        if (tile[i] >= 0) key[i] = mode == 0 ? ranges[tile[i]].y - ranges[tile[i]].x : todo[tile[i]];
+        if (tile[i] >= 0) key[i] = key_of(tile[i]);
         m = key[i] > m ? key[i] : m;
     }
     if (m) atomicMax(&smax, m);
@@ -97,6 +99,22 @@ __global__ void __launch_bounds__(1024) tile_order_kernel(int mode, int gx, int 
     for (int i = 0; i < PER; i++)
         if (tile[i] != -2) order[(size_t)x * per_xcd + atomicAdd(&base[bucket[i]], 1u)] = tile[i] >= 0 ? (uint32_t)tile[i] : 0xFFFFFFFFu;
 }
+__global__ void __launch_bounds__(1024) tile_order_kernel(int mode, int gx, int gy, int bh, int per_xcd, const uint2* __restrict__ ranges,
+                                                          const uint32_t* __restrict__ todo, uint32_t* __restrict__ order) {
+    __shared__ uint32_t hist[256], base[256], smax;
+    tile_order_body(hist, base, smax, blockIdx.x, gx, gy, bh, per_xcd, order,
+                    [&](int tile) -> uint32_t { return mode == 0 ? ranges[tile].y - ranges[tile].x : todo[tile]; });
+}
+// The scan of the tiles' pair counts into their ranges and the forward's tile order in ONE grid (the chain of a frame whose projection
+// counted, binning.hip): both need nothing but the counts -- the order's key is the tile's list length, and that IS its count (a tile
+// whose list the capacity mode drops keeps its count as the key: the order only decides dispatch).  Workgroups 0..7: the XCDs' orders
+// (none when per_xcd == 0), the last workgroup: the scan.
+__global__ void __launch_bounds__(1024) tile_scan_order_kernel(const uint32_t* __restrict__ cnt, uint32_t ntiles, uint2* __restrict__ ranges, uint32_t cap,
+                                                               int gx, int gy, int bh, int per_xcd, uint32_t* __restrict__ order) {
+    __shared__ uint32_t hist[256], base[256], smax, wsum[16];
+    if (blockIdx.x == gridDim.x - 1) tile_scan_body(wsum, cnt, ntiles, ranges, nullptr, cap);
+    else tile_order_body(hist, base, smax, blockIdx.x, gx, gy, bh, per_xcd, order, [&](int tile) -> uint32_t { return cnt[tile]; });
+}
 
 // The exponent of a blended Gaussian, written so that EVERY kernel that evaluates it rounds it the same way (the forward decides
 // alpha >= 1/255 and T < 1e-4 from it, the backward has to take the same decisions): -0.5 * (dx*(dx*cxx) + dy*(dy*cyy)) - dy*(dx*cxy),
@@ -124,6 +142,23 @@ __device__ __forceinline__ v2f blend_power2(float u1, float cx, float cyy, v2f d
     const v2f q = u1 + u2;
     return __builtin_elementwise_fma(q, v2f{-0.5f, -0.5f}, -c2);
 }
+// ... and element-wise for TWO Gaussians at one pixel (render_fwd_kernel<1>: the entries j and j + 1 of a list): per element the operations
+// of blend_power_xx / blend_power_xy / blend_power, in their order
+__device__ __forceinline__ v2f blend_power_xx_e2(v2f cxx, v2f dx) {
+#pragma clang fp contract(off)
+    return dx * (dx * cxx);
+}
+__device__ __forceinline__ v2f blend_power_xy_e2(v2f cxy, v2f dx) {
+#pragma clang fp contract(off)
+    return dx * cxy;
+}
+__device__ __forceinline__ v2f blend_power_e2(v2f u1, v2f cx, v2f cyy, v2f dy) {
+#pragma clang fp contract(off)
+    const v2f u2 = dy * (dy * cyy);
+    const v2f c2 = dy * cx;
+    const v2f q = u1 + u2;
+    return __builtin_elementwise_fma(q, v2f{-0.5f, -0.5f}, -c2);
+}
 
 // what both blending kernels take first: the image's tile grid and the block -> tile map
 struct BlendHead {
@@ -141,12 +176,22 @@ struct RenderArgs : BlendHead {
     float4* zfill; uint32_t zfill_n4;        // opt: a range zero-filled on the way (fdgs_raster_params::acc_zero: the backward's accumulator)
 };
 
+// FORM (knob blend_fwd_form) = the inner loop.  0: one list entry per trip, staged as its three records.  1: the entries j and j + 1 per trip.
+// What does not depend on the pixel's T -- both exponents, both alphas, 1 - alpha -- is evaluated for the two at once in packed f32 (one
+// v_pk_* per operation and PAIR: the element-wise forms above, the roundings of form 0), speculatively for j + 1; then the part that depends
+// on T runs for j and, unless the pixel stopped there, for j + 1, as form 0 does.  The three decisions (power > 0, alpha < 1/255,
+// T (1 - alpha) < 1e-4) see the values form 0 computes, so every output bit is form 0's.  A round is staged as 128 pair records of five
+// float4 -- (x x' y y') (cxx cxx' cxy cxy') (cyy cyy' opacity opacity') (r g b depth) (r' g' b' depth') -- so that the packed operands are the
+// register pairs the reads deliver, read at five immediate offsets from one running address.  An odd list end: the entry behind it is
+// staged as a copy of the last one (gid_of) and masked out of the sequential part.
+template <int FORM>
 __global__ void __launch_bounds__(256) render_fwd_kernel(RenderArgs a) {
     if (a.zfill)     // (the kernel is bound by its arithmetic: ~one 16-byte store per thread rides along for free, and a fill launch is gone)
         for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < a.zfill_n4; k += gridDim.x * 256u) a.zfill[k] = make_float4(0.f, 0.f, 0.f, 0.f);
     const int tile = unit_lookup(a.order, a.per_xcd, blockIdx.x, a.gx, a.gy, 1, a.bh);
     if (tile < 0) return;
-    __shared__ float4 sA[256], sB[256], sC[256];
+    __shared__ float4 sRec[FORM == 1 ? 640 : 768];
+    float4 *const sA = sRec, *const sB = sRec + 256, *const sC = sRec + 512;      // (form 0)
     __shared__ uint32_t sTodo[4];
     const int t = threadIdx.x;
     const int x = (tile % a.gx) * TILE + (t & 15), y = (tile / a.gx) * TILE + (t >> 4);
@@ -157,7 +202,8 @@ __global__ void __launch_bounds__(256) render_fwd_kernel(RenderArgs a) {
     const int rounds = (toDo + 255) / 256;
     bool done = !inside;
     float T = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f, Dp = 0.f;
-    uint32_t contributor = 0, last = 0;
+    [[maybe_unused]] uint32_t contributor = 0;       // (form 0's count of the entries passed; form 1 derives it from the round and j)
+    uint32_t last = 0;
     // staging pipeline (round 6; the backward has had it since round 3): list ids two rounds ahead, records one round ahead (the records'
     // addresses depend on the ids) -- the two dependent memory round trips of a round no longer sit between its barrier and its arithmetic
     const int n_list = (int)(range.y - range.x);
@@ -174,27 +220,73 @@ __global__ void __launch_bounds__(256) render_fwd_kernel(RenderArgs a) {
     }
     for (int r = 0; r < rounds; r++, toDo -= 256) {
         if (__syncthreads_count(done) == 256) break;
-        sA[t] = rA; sB[t] = rB; sC[t] = rC;      // (entries behind the end of the list are copies of its last entry: never read, j < lim)
+        if constexpr (FORM == 1) {               // entry t = half t & 1 of pair record t >> 1
+            float* rec = reinterpret_cast<float*>(sRec + 5 * (t >> 1)) + (t & 1);
+            rec[0] = rA.x; rec[2] = rA.y; rec[4] = rA.z; rec[6] = rA.w; rec[8] = rB.x; rec[10] = rB.y;
+            sRec[5 * (t >> 1) + 3 + (t & 1)] = make_float4(rC.x, rC.y, rC.z, rB.z);
+        } else {
+            sA[t] = rA; sB[t] = rB; sC[t] = rC;  // (entries behind the end of the list are copies of its last entry: never read, j < lim)
+        }
         __syncthreads();
         if (r + 1 < rounds) { g_cur = g_nxt; rA = a.recA[g_cur]; rB = a.recB[g_cur]; rC = a.recC[g_cur]; }
         if (r + 2 < rounds) g_nxt = gid_of(r + 2);
         const int lim = toDo < 256 ? toDo : 256;
-        for (int j = 0; !done && j < lim; j++) {
-            contributor++;
-            const float4 A = sA[j];
-            const float4 B = sB[j];
-            const float dx = A.x - pxf, dy = A.y - pyf;
-            const float power = blend_power(blend_power_xx(A.z, dx), blend_power_xy(A.w, dx), B.x, dy);
-            if (power > 0.0f) continue;
-            const float alpha = fminf(FDGS_ALPHA_MAX, B.y * __expf(power));
-            if (alpha < FDGS_ALPHA_MIN) continue;
-            const float test_T = T * (1.0f - alpha);
-            if (test_T < FDGS_T_STOP) { done = true; continue; }
-            const float4 Cc = sC[j];
-            const float w = alpha * T;
-            C0 += Cc.x * w; C1 += Cc.y * w; C2 += Cc.z * w; Dp += B.z * w;
-            T = test_T;
-            last = contributor;
+        if constexpr (FORM == 1) {
+            const uint32_t first = (uint32_t)r * 256u;       // entries in front of this round: form 0's `contributor` at entry j is first + j + 1
+            const float4* q = sRec;
+            for (int j = 0; !done && j < lim; j += 2, q += 5) {
+                const float4 Q0 = q[0], Q1 = q[1], Q2 = q[2];
+                float4 E0 = q[3];
+                const float4 E1 = q[4];
+                const v2f dx = v2f{Q0.x, Q0.y} - pxf, dy = v2f{Q0.z, Q0.w} - pyf;
+                const v2f power = blend_power_e2(blend_power_xx_e2(v2f{Q1.x, Q1.y}, dx), blend_power_xy_e2(v2f{Q1.z, Q1.w}, dx), v2f{Q2.x, Q2.y}, dy);
+                v2f alpha = v2f{Q2.z, Q2.w} * v2f{__expf(power[0]), __expf(power[1])};
+                alpha[0] = fminf(FDGS_ALPHA_MAX, alpha[0]); alpha[1] = fminf(FDGS_ALPHA_MAX, alpha[1]);
+                const v2f om = 1.0f - alpha;
+                // (keeps the read of E0 with the four others at the top of the trip: sunk into the branch below it is a read of its own, with
+                // its own address move and a full wait, in front of the first accumulation)
+                asm volatile("" : "+v"(E0.x), "+v"(E0.y), "+v"(E0.z), "+v"(E0.w));
+                if (!(power[0] > 0.0f) && !(alpha[0] < FDGS_ALPHA_MIN)) {
+                    const float test_T = T * om[0];
+                    if (test_T < FDGS_T_STOP) {
+                        done = true;
+                    } else {
+                        const float w = alpha[0] * T;
+                        C0 += E0.x * w; C1 += E0.y * w; C2 += E0.z * w; Dp += E0.w * w;
+                        T = test_T;
+                        last = first + (uint32_t)j + 1u;
+                    }
+                }
+                if (!done && j + 1 < lim && !(power[1] > 0.0f) && !(alpha[1] < FDGS_ALPHA_MIN)) {
+                    const float test_T = T * om[1];
+                    if (test_T < FDGS_T_STOP) {
+                        done = true;
+                    } else {
+                        const float w = alpha[1] * T;
+                        C0 += E1.x * w; C1 += E1.y * w; C2 += E1.z * w; Dp += E1.w * w;
+                        T = test_T;
+                        last = first + (uint32_t)j + 2u;
+                    }
+                }
+            }
+        } else {
+            for (int j = 0; !done && j < lim; j++) {
+                contributor++;
+                const float4 A = sA[j];
+                const float4 B = sB[j];
+                const float dx = A.x - pxf, dy = A.y - pyf;
+                const float power = blend_power(blend_power_xx(A.z, dx), blend_power_xy(A.w, dx), B.x, dy);
+                if (power > 0.0f) continue;
+                const float alpha = fminf(FDGS_ALPHA_MAX, B.y * __expf(power));
+                if (alpha < FDGS_ALPHA_MIN) continue;
+                const float test_T = T * (1.0f - alpha);
+                if (test_T < FDGS_T_STOP) { done = true; continue; }
+                const float4 Cc = sC[j];
+                const float w = alpha * T;
+                C0 += Cc.x * w; C1 += Cc.y * w; C2 += Cc.z * w; Dp += B.z * w;
+                T = test_T;
+                last = contributor;
+            }
         }
     }
     if (inside) {
@@ -680,14 +772,29 @@ __global__ void __launch_bounds__(64) render_bwd_strip_kernel(RenderBwdArgs a) {
     }
 }
 
-// launches tile_order_kernel when the knob is on and an XCD's tiles fit its LDS sort; returns the order to hand to the kernel (or nullptr)
+// do the blending kernels of this image take their tiles heaviest-first (the knob is on and an XCD's tiles fit its LDS sort)?
+static bool tiles_ordered(const ImgLayout& il) { return g_tune.tile_order && il.per_xcd <= TILE_ORDER_MAX && il.per_xcd >= 1; }
+
+// launches tile_order_kernel where tiles_ordered; returns the order to hand to the kernel (or nullptr)
 static const uint32_t* make_tile_order(hipStream_t stream, int mode, const ImgLayout& il, const void* img, void* img_w) {
-    if (!g_tune.tile_order || il.per_xcd > TILE_ORDER_MAX || il.per_xcd < 1) return nullptr;
+    if (!tiles_ordered(il)) return nullptr;
     uint32_t* order = at<uint32_t>(img_w, mode == 0 ? il.order_f : il.order_b);
     FDGS_TIMED("tile_order", stream);
     hipLaunchKernelGGL(tile_order_kernel, dim3(8), dim3(1024), 0, stream, mode, il.gx, il.gy, XCD_ROWS, il.per_xcd, at<uint2>(img, il.ranges),
                        at<uint32_t>(img, il.todo), order);
     return order;
+}
+
+int launch_tile_scan_order(hipStream_t stream, const ImgLayout& il, const uint32_t* counts, void* img, uint32_t cap, int debug, bool* order_made) {
+    const bool ordered = tiles_ordered(il);
+    {
+        FDGS_TIMED("tile_scan", stream);
+        hipLaunchKernelGGL(tile_scan_order_kernel, dim3(ordered ? 9 : 1), dim3(1024), 0, stream, counts, (uint32_t)(il.gx * il.gy), at<uint2>(img, il.ranges), cap,
+                           il.gx, il.gy, XCD_ROWS, il.per_xcd, at<uint32_t>(img, il.order_f));
+    }
+    FDGS_LAUNCH_CHECK("tile_scan", debug, stream);
+    if (order_made) *order_made = ordered;
+    return FDGS_OK;
 }
 
 // what both blending launchers set from the frame's buffers (Args = RenderArgs with a writable img, RenderBwdArgs with a const one);
@@ -720,8 +827,9 @@ static void launch_render_bwd(hipStream_t stream, int ppl, bool depth, const Ren
 
 using namespace fdgs;
 
-extern "C" int fdgs_render_fwd(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, void* img,
-                               uint32_t R, float* out_color, float* out_depth) {
+namespace fdgs {
+int render_fwd_impl(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, void* img, uint32_t R, float* out_color,
+                    float* out_depth, bool order_made) {
     int rc = validate_raster_params(p);
     if (rc) return rc;
     FDGS_REQUIRE(geom && img && out_color && out_depth && (binning || R == 0), "NULL buffer");
@@ -731,13 +839,19 @@ extern "C" int fdgs_render_fwd(void* stream_, const fdgs_raster_params* p, const
     a.out_color = out_color; a.out_depth = out_depth;
     a.tile_todo = at<uint32_t>(img, il.todo);
     a.zfill = reinterpret_cast<float4*>(p->acc_zero); a.zfill_n4 = (uint32_t)p->P * 4u;
-    a.order = R > 0 ? make_tile_order(stream, 0, il, img, img) : nullptr;
+    a.order = R == 0 ? nullptr : order_made ? at<uint32_t>(img, il.order_f) : make_tile_order(stream, 0, il, img, img);
     {
         FDGS_TIMED("render_fwd", stream);
-        hipLaunchKernelGGL(render_fwd_kernel, dim3(unit_grid(a.gx, a.gy, 1, a.bh)), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(g_tune.blend_fwd_form == 1 ? render_fwd_kernel<1> : render_fwd_kernel<0>, dim3(unit_grid(a.gx, a.gy, 1, a.bh)), dim3(256), 0, stream, a);
     }
     FDGS_LAUNCH_CHECK("render_fwd", p->debug, stream);
     return FDGS_OK;
+}
+}  // namespace fdgs
+
+extern "C" int fdgs_render_fwd(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, void* img,
+                               uint32_t R, float* out_color, float* out_depth) {
+    return render_fwd_impl(stream_, p, geom, binning, img, R, out_color, out_depth, false);
 }
 
 extern "C" int fdgs_render_pick(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
@@ -758,7 +872,7 @@ extern "C" int fdgs_render_pick(void* stream_, const fdgs_raster_params* p, cons
     a.alpha_cut = alpha_cut; a.row_map = row_map_opt;
     a.pick_id = out->pick_id; a.pick_weight = out->pick_weight; a.surface_id = out->surface_id; a.surface_depth = out->surface_depth;
     // the forward's own heaviest-first order, where fdgs_render_fwd wrote one (make_tile_order's condition); never rebuilt here
-    const bool ordered = !a.empty && g_tune.tile_order && il.per_xcd <= TILE_ORDER_MAX && il.per_xcd >= 1;
+    const bool ordered = !a.empty && tiles_ordered(il);
     a.order = ordered ? at<uint32_t>(img, il.order_f) : nullptr;
     {
         FDGS_TIMED("render_pick", stream);

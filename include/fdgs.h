@@ -43,7 +43,7 @@ int fdgs_abi_version(void);
  * roofline measurement).  fdgs_timing_report synchronises the device and writes "kernel_name count total_ms" lines. */
 int fdgs_timing_enable(int on);
 int fdgs_timing_report(char* buf, size_t buflen, int reset);
-/* Development / test knobs (ABI 4; ten since ABI 5, eleven since round 6, thirteen with bin_form and tile_sort_cap).  The library holds ONE table of integer knobs; it is filled from the environment variables
+/* Development / test knobs (ABI 4; ten since ABI 5, eleven since round 6, thirteen with bin_form and tile_sort_cap, fifteen with bin_count and blend_fwd_form).  The library holds ONE table of integer knobs; it is filled from the environment variables
  * FDGS_<NAME> once, when the library is loaded, and afterwards changes only through fdgs_tuning_set -- no entry point reads the
  * environment.  Knobs select between equivalent kernel forms or launch shapes (same results up to summation order), never semantics:
  *   d1_form (0 | 8 | 16 | 32), d1_wgs, d1_split, skip_dead, d4_mfma, d4_rows_kb, tile_cull (0 = the reference's rectangle lists), rbwd_ppl (-1 = by image size | 4 | 2 | 0),
@@ -53,7 +53,11 @@ int fdgs_timing_report(char* buf, size_t buflen, int reset);
  *   32-row kernel everywhere),
  *   bin_form (0 = depth sort of the Gaussians + pair expansion + global tile sort, 1 = pairs placed per tile + one LDS sort per tile --
  *   images of up to 16 384 tiles, larger ones keep form 0 --, -1 = by shape; same lists bit for bit), tile_sort_cap (bin_form 1: list
- *   length above which a tile's sort takes the chunk-and-merge path; 0 = the compiled LDS capacity, 4 096; lower values are for tests).
+ *   length above which a tile's sort takes the chunk-and-merge path; 0 = the compiled LDS capacity, 4 096; lower values are for tests),
+ *   bin_count (bin_form 1, fdgs_raster_fwd_capacity only: 0 = the tiles' pairs are counted by a launch of its own, 1 = by the projection
+ *   kernel -- images of up to 5 632 tiles --, with the scan of the counts and the forward's tile order in one launch, 2 = as 1 at every
+ *   tile count form 1 runs at; same lists bit for bit; the staged calls always count in fdgs_bin_sort), blend_fwd_form (inner loop of the
+ *   blending forward: 0 = one list entry per trip, 1 = two per trip in packed f32; same image, depth and per-pixel state bit for bit).
  * `name` is the lower- or upper-case knob name, with or without the FDGS_ prefix.  Process-global, not thread-safe against running calls:
  * set knobs between frames.  fdgs_tuning_reset restores the load-time values.  See INTEGRATION.md ("Knobs"). */
 int fdgs_tuning_set(const char* name, int value);

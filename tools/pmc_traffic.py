@@ -16,7 +16,8 @@ from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ALIAS = {"radix_digit_scan": "radix_scan", "scan_chunk": "scan_tiles", "scan_add": "scan_tiles", "adam": "adam_step",
-         "deform_plane_grad_mfma": "deform_plane_grad", "deform_fwd16": "deform_fwd", "deform_mlp_ws": "deform_fwd", "deform_bwd_data_ws": "deform_bwd_data", "pack_weights16": "pack_weights"}
+         "deform_plane_grad_mfma": "deform_plane_grad", "deform_fwd16": "deform_fwd", "deform_mlp_ws": "deform_fwd", "deform_bwd_data_ws": "deform_bwd_data", "pack_weights16": "pack_weights",
+         "tile_scan_order": "tile_scan"}
 
 
 def src_sha16():
@@ -61,7 +62,7 @@ def main():
     else:
         fe, wr = per_launch(fetch_dir, "FETCH_SIZE"), per_launch(write_dir, "WRITE_SIZE")
     res = {"_workload": workload, "_src_sha16": src_sha16(),
-           "_source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --workload "
+           "_source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, counters only: no tracing in the same run) -- python bench.py --workload "
                       + workload + " --steps 3 --warmup 2 --repeats 1 --no-cpu-baseline --no-extras, MI355X",
            "_units": "KB per launch as reported by rocprofv3 (TCC_EA0 request counters x 64 B); gfx950 reports HALF of the bytes of "
                      "16-B/lane streaming reads (MI355X_MICROARCH.md, HBM section): consumers double FETCH_SIZE"}
