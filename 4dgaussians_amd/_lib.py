@@ -112,6 +112,10 @@ class PickOut(Structure):
     _fields_ = [("pick_id", c_void_p), ("pick_weight", c_void_p), ("surface_id", c_void_p), ("surface_depth", c_void_p)]
 
 
+class ContribRow(Structure):         # fdgs_contrib_row: one [N,4] int32 tensor row
+    _fields_ = [("weight_sum", c_float), ("weight_max", c_float), ("pixels", c_uint32), ("tiles", c_uint32)]
+
+
 # every symbol include/fdgs.h declares: (restype, argtypes)
 SYMBOLS = {
     "fdgs_last_error": (c_char_p, []),
@@ -189,6 +193,7 @@ SYMBOLS = {
     "fdgs_motion_resolve": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "fdgs_motion_resolve_host": (c_int, [c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "fdgs_render_pick": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_uint32, c_float, c_void_p, POINTER(PickOut)]),
+    "fdgs_render_contrib": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p]),
 }
 CURVES = {"hilbert": 0, "morton": 1}      # FDGS_CURVE_*
 RGB8_MODES = {"trunc": 0, "round": 1}     # FDGS_RGB8_*

@@ -28,8 +28,8 @@ import torch
 from . import _lib
 from . import deformation as _deformation
 from . import sh as _sh
-from .playback import (_MOTION_DOC, _PICK_DOC, BakedFrame, SparseBaked, _carve, _checked_interp, _field_mask, _field_slots, _locate,
-                       _perm_maps, _render_motion_state, _render_pick_state, _render_state, _state_arrays)
+from .playback import (_CONTRIB_DOC, _MOTION_DOC, _PICK_DOC, BakedFrame, SparseBaked, _carve, _checked_interp, _field_mask, _field_slots,
+                       _locate, _perm_maps, _render_contrib_state, _render_motion_state, _render_pick_state, _render_state, _state_arrays)
 
 WRAPS = ("clamp", "loop", "pingpong")
 _SH_ZERO = 1e-13        # entries of a band matrix below this are structural zeros of the rotation (the solve leaves ~1e-16 there)
@@ -303,6 +303,15 @@ class Composite:
 
     render_pick.__doc__ = _PICK_DOC + """
         The ids are rows of the whole scene (sum(N), model m's at `slices[m]`): `model_of_rows` splits them into (model, row)."""
+
+    def render_contrib(self, viewpoint_camera, pipe, bg_color, into=None, pixel_weight=None, scaling_modifier=1.0, cam_type=None,
+                       interp="linear", rgb8=None):
+        return _render_contrib_state("Composite.render_contrib", self, lambda t: self.state_at(t, interp), self.active_sh_degree, self.device,
+                                     *self._maps, viewpoint_camera, pipe, bg_color, into, pixel_weight, scaling_modifier, cam_type, rgb8)
+
+    render_contrib.__doc__ = _CONTRIB_DOC + """
+        The rows are rows of the whole scene (sum(N), model m's at `slices[m]`; `model_of_rows` splits row indices into (model, row)).
+        (There is no Composite.select_rows: select per model with `Baked.select_rows`, then compose again.)"""
 
     def _make_pick_row_map(self):
         """The stored -> scene row map of fdgs_render_pick: model m's segment is offset_m + perm_m (offset_m + arange for a model stored in

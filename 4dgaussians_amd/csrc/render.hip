@@ -10,6 +10,8 @@
 // slower and was dropped in round 3.)
 // Pick pass (render_pick_kernel): the forward's layout once more over a finished frame's lists, for the id of the Gaussian with the largest
 // blend weight and the id and depth of the one at which the accumulated alpha reaches a cut; it writes nothing into the frame.
+// Contribution pass (render_contrib_kernel): that walk again, reduced per Gaussian instead of per pixel -- the sum and the maximum of the
+// blend weight over the pixels, the pixels and the tiles that show it --, one atomic record per (tile, entry); it writes nothing into the frame.
 // Tile rows are dealt to the XCDs in groups (unit_of_block: workgroup b runs on XCD b % 8), so that neighbouring tiles -- which list
 // the same Gaussians -- share an XCD's 4 MiB L2 and every XCD owns rows from the whole height of the image.
 // Replaces renderCUDA forward/backward of the un-vendored rasterizer (Appendix B.3/B.4).
@@ -434,6 +436,179 @@ __device__ __forceinline__ float row_allsum(float v) {
     v += dpp_f<0x141>(v);  // row_half_mirror      : other quad of the 8
     v += dpp_f<0x140>(v);  // row_mirror           : other half of the 16
     return v;
+}
+
+// the largest of an unsigned word over the 64 lanes of a wave, wave_allsum's moves; every lane ends with it.  (The contribution pass takes
+// the maximum of floats >= +0 on their BITS: fmaxf quiets its operands first, three instructions per step where v_max_u32 folds the DPP move.)
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_u(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true);
+}
+__device__ __forceinline__ uint32_t umax2(uint32_t a, uint32_t b) { return a > b ? a : b; }
+__device__ __forceinline__ uint32_t wave_allmax_u(uint32_t v) {
+    v = umax2(v, dpp_u<0xB1>(v));
+    v = umax2(v, dpp_u<0x4E>(v));
+    v = umax2(v, dpp_u<0x141>(v));
+    v = umax2(v, dpp_u<0x140>(v));
+    {
+        auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+        v = umax2(r[0], r[1]);
+    }
+    {
+        auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+        v = umax2(r[0], r[1]);
+    }
+    return v;
+}
+
+// ---- the contribution pass: how much every Gaussian adds to the image ------------------------------------------------------------------
+// The pick pass's walk once more (its layout, staging pipeline, tile order and expressions, compiled without contraction: w has the bits of
+// the forward's w), but what leaves the kernel is per GAUSSIAN, not per pixel: the sum and the maximum of v = w * pixel_weight over the
+// pixels, the number of pixels with v > 0 and the number of tiles that hold one.  That is the blending backward's shape with three values
+// per hit in place of nine: for a staged entry a wave in which no lane has v > 0 does nothing; otherwise it finishes sum, maximum and
+// count over its 64 lanes in registers (DPP inside the rows, permlane swaps across them, a ballot's popcount) and lane 0 leaves them
+// in the wave's own LDS slot sAcc[entry][wave] with ONE plain 16-byte store (no LDS atomics: ds_add_f32 sustains 0.33 lanes/clk/CU).  After the
+// round the workgroup adds the four slots of every entry and issues at most ONE atomic per word of the Gaussian's 16-byte record and
+// (tile, entry): four neighbouring lanes own the four words of one record -- f32 add, u32 max on the float's bits (v >= +0: the
+// unsigned order of the bits is the order of the values), u32 add, u32 add of 1 -- so one wave's atomics of a pass cover 16 whole
+// records.  (FDGS_CONTRIB_FLUSH_LANES = 1 at build time is the form it was measured against: one lane per record, four atomic
+// instructions, each touching one word of 64 different records -- the same kernel time within 1 %, 0.212 against 0.213 ms on config 4:
+// the flush is not where the time goes, the per-entry reductions are)  The walk loop runs to the WAVE's longest n_contrib so that every lane
+// takes part in the reductions; a lane past its own end contributes v = 0.  Nothing of the frame is written.
+#ifndef FDGS_CONTRIB_FLUSH_LANES
+#define FDGS_CONTRIB_FLUSH_LANES 4
+#endif
+struct ContribArgs : BlendHead {
+    const uint32_t* tile_todo;               // per tile: max n_contrib, the forward's walk length
+    const uint2* ranges; const uint32_t* pair_gid;
+    const float4 *recA, *recB, *recC;
+    const float* bg;
+    const float* final_T; const uint32_t* n_contrib;
+    uint32_t R; int P;                       // what the lists were laid out for: fences for a stale img
+    const float* pixel_weight;               // opt [H*W]
+    const int32_t* row_map;                  // opt [P]: the record Gaussian g is accumulated into
+    uint32_t* rows;                          // [P] records of four words: weight_sum (f32), weight_max (f32), pixels, tiles
+};
+
+__global__ void __launch_bounds__(256) render_contrib_kernel(ContribArgs a) {
+#pragma clang fp contract(off)
+    const int tile = unit_lookup(a.order, a.per_xcd, blockIdx.x, a.gx, a.gy, 1, a.bh);
+    if (tile < 0 || tile >= a.gx * a.gy) return;
+    __shared__ float4 sA[256], sB[256];
+    __shared__ uint32_t sG[256];
+    __shared__ uint4 sAcc[256 * 4];          // [entry][wave]: the bits of the sum, the bits of the maximum, the count, unused
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int x = (tile % a.gx) * TILE + (t & 15), y = (tile / a.gx) * TILE + (t >> 4);
+    const bool inside = x < a.W && y < a.H;
+    const float pxf = (float)x, pyf = (float)y;
+    const size_t pix = (size_t)y * a.W + x;
+    uint2 range = a.ranges[tile];
+    range.y = range.y < a.R ? range.y : a.R;
+    range.x = range.x < range.y ? range.x : range.y;
+    const uint32_t walk = a.tile_todo[tile];
+    uint32_t own = inside ? a.n_contrib[pix] : 0u;
+    float m = 1.0f;
+    if (a.pixel_weight) {
+        m = inside ? a.pixel_weight[pix] : 0.0f;
+        if (!(m > 0.0f)) own = 0u;           // zero, negative, NaN: no v of this pixel is > 0
+    }
+    const int n_list = (int)(range.y - range.x);
+    const int todo = walk < (uint32_t)n_list ? (int)walk : n_list;           // the tile's walk length, clamped to the list ...
+    const int mine = own < (uint32_t)todo ? (int)own : todo;                // ... and this lane's, clamped to the tile's
+    const int rounds = (todo + 255) / 256;
+    int wave_mine = mine;                                                    // the longest walk among the wave's 64 pixels
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const int u = __shfl_xor(wave_mine, o, 64); wave_mine = u > wave_mine ? u : wave_mine; }
+    float T = 1.0f;
+    int seen = 0;                            // entries of the list this lane has passed
+    auto gid_of = [&](int r) -> uint32_t {
+        const int e = r * 256 + t;
+        return a.pair_gid[range.x + (e < n_list ? e : n_list - 1)];
+    };
+    uint32_t g_cur = 0u, g_nxt = 0u;
+    float4 rA, rB;
+    if (rounds > 0) {
+        g_cur = gid_of(0);
+        if (rounds > 1) g_nxt = gid_of(1);
+        rA = a.recA[g_cur]; rB = a.recB[g_cur];
+    }
+    for (int r = 0; r < rounds; r++) {
+        if (__syncthreads_count(seen >= mine) == 256) break;
+        const int left = todo - r * 256;
+        const int staged = left < 256 ? left : 256;                         // entries of this round
+        sA[t] = rA; sB[t] = rB; sG[t] = g_cur;
+        for (int k = t; k < staged * 4; k += 256) sAcc[k] = make_uint4(0u, 0u, 0u, 0u);      // (an entry a wave does not hit keeps a zero slot)
+        __syncthreads();
+        if (r + 1 < rounds) { g_cur = g_nxt; rA = a.recA[g_cur]; rB = a.recB[g_cur]; }
+        if (r + 2 < rounds) g_nxt = gid_of(r + 2);
+        const int rem = mine - seen;
+        const int wave_rem = wave_mine - seen;
+        const int lim = wave_rem < staged ? wave_rem : staged;
+        for (int j = 0; j < lim; j++) {
+            float v = 0.0f;
+            if (j < rem) {
+                const float4 Aj = sA[j];
+                const float4 B = sB[j];
+                const float dx = Aj.x - pxf, dy = Aj.y - pyf;
+                const float power = blend_power(blend_power_xx(Aj.z, dx), blend_power_xy(Aj.w, dx), B.x, dy);
+                if (!(power > 0.0f)) {
+                    const float alpha = fminf(FDGS_ALPHA_MAX, B.y * __expf(power));
+                    if (!(alpha < FDGS_ALPHA_MIN)) {
+                        const float w = alpha * T;
+                        v = w * m;
+                        T = T * (1.0f - alpha);
+                    }
+                }
+            }
+            const bool hit = v > 0.0f;
+            const unsigned long long hits = __ballot(hit);
+            if (hits == 0ull) continue;                                      // (uniform over the wave)
+            v = hit ? v : 0.0f;
+            const float s = wave_allsum(v);
+            const uint32_t mx = wave_allmax_u(__float_as_uint(v));           // (v >= +0: the order of the bits is the order of the values)
+            if (lane == 0) sAcc[j * 4 + wv] = make_uint4(__float_as_uint(s), mx, (uint32_t)__popcll(hits), 0u);      // no other writer
+        }
+        seen += 256;
+        __syncthreads();
+        auto record_of = [&](int jj) -> uint32_t* {                          // where entry jj is accumulated, nullptr: dropped
+            const uint32_t g = sG[jj];
+            if (g >= (uint32_t)a.P) return nullptr;
+            const uint32_t row = a.row_map ? (uint32_t)a.row_map[g] : g;
+            return row < (uint32_t)a.P ? a.rows + (size_t)row * 4 : nullptr;
+        };
+#if FDGS_CONTRIB_FLUSH_LANES == 4
+        const int sub = t & 3;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int jj = i * 64 + (t >> 2);
+            if (jj >= staged) continue;
+            const uint4 q0 = sAcc[jj * 4], q1 = sAcc[jj * 4 + 1], q2 = sAcc[jj * 4 + 2], q3 = sAcc[jj * 4 + 3];
+            const uint32_t c = (q0.z + q1.z) + (q2.z + q3.z);
+            if (c == 0u) continue;
+            uint32_t* rec = record_of(jj);
+            if (!rec) continue;
+            if (sub == 0) {
+                atomicAdd(reinterpret_cast<float*>(rec), (__uint_as_float(q0.x) + __uint_as_float(q1.x)) + (__uint_as_float(q2.x) + __uint_as_float(q3.x)));
+            } else if (sub == 1) {
+                atomicMax(rec + 1, umax2(umax2(q0.y, q1.y), umax2(q2.y, q3.y)));
+            } else {
+                atomicAdd(rec + sub, sub == 2 ? c : 1u);
+            }
+        }
+#else
+        if (t < staged) {
+            const uint4 q0 = sAcc[t * 4], q1 = sAcc[t * 4 + 1], q2 = sAcc[t * 4 + 2], q3 = sAcc[t * 4 + 3];
+            const uint32_t c = (q0.z + q1.z) + (q2.z + q3.z);
+            uint32_t* rec = c ? record_of(t) : nullptr;
+            if (rec) {
+                atomicAdd(reinterpret_cast<float*>(rec), (__uint_as_float(q0.x) + __uint_as_float(q1.x)) + (__uint_as_float(q2.x) + __uint_as_float(q3.x)));
+                atomicMax(rec + 1, umax2(umax2(q0.y, q1.y), umax2(q2.y, q3.y)));
+                atomicAdd(rec + 2, c);
+                atomicAdd(rec + 3, 1u);
+            }
+        }
+#endif
+    }
 }
 
 // Sums of ten values over the 64 lanes of a wave as a reduce-scatter.  xor-1 and xor-2 butterflies inside the quads halve the values
@@ -879,6 +1054,31 @@ extern "C" int fdgs_render_pick(void* stream_, const fdgs_raster_params* p, cons
         hipLaunchKernelGGL(render_pick_kernel, dim3(unit_grid(a.gx, a.gy, 1, a.bh)), dim3(256), 0, stream, a);
     }
     FDGS_LAUNCH_CHECK("render_pick", p->debug, stream);
+    return FDGS_OK;
+}
+
+extern "C" int fdgs_render_contrib(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
+                                   uint32_t R, const float* pixel_weight_opt, const int32_t* row_map_opt, fdgs_contrib_row* rows) {
+    FDGS_REQUIRE(p && geom && binning && img && rows, "NULL pointer (params, geom, binning, img and rows)");
+    FDGS_REQUIRE(p->P >= 0 && p->W >= 1 && p->H >= 1, "bad P/W/H");
+    FDGS_REQUIRE((p->W + TILE - 1) / TILE < 65536 && (p->H + TILE - 1) / TILE < 65536, "image too large");
+    FDGS_REQUIRE(aligned_to(rows, 16), "rows must be 16-byte aligned");
+    FDGS_REQUIRE(aligned_to(pixel_weight_opt, 4) && aligned_to(row_map_opt, 4), "pixel_weight_opt and row_map_opt must be 4-byte aligned");
+    if (p->P == 0 || R == 0) return FDGS_OK;          // nothing was blended: nothing is accumulated, nothing is launched
+    hipStream_t stream = (hipStream_t)stream_;
+    ContribArgs a{};
+    const ImgLayout il = fill_blend_args(a, p, geom, binning, img, R);
+    a.tile_todo = at<uint32_t>(img, il.todo);
+    a.R = R; a.P = p->P;
+    a.pixel_weight = pixel_weight_opt; a.row_map = row_map_opt;
+    a.rows = reinterpret_cast<uint32_t*>(rows);
+    // the forward's own heaviest-first order, where fdgs_render_fwd wrote one (make_tile_order's condition); never rebuilt here
+    a.order = tiles_ordered(il) ? at<uint32_t>(img, il.order_f) : nullptr;
+    {
+        FDGS_TIMED("render_contrib", stream);
+        hipLaunchKernelGGL(render_contrib_kernel, dim3(unit_grid(a.gx, a.gy, 1, a.bh)), dim3(256), 0, stream, a);
+    }
+    FDGS_LAUNCH_CHECK("render_contrib", p->debug, stream);
     return FDGS_OK;
 }
 

@@ -34,6 +34,15 @@ row and view depth of the one at which the pixel turns opaque -- for one extra w
 
     out = baked.render_pick(cam, pipe, background)                            # out["pick_id"], out["surface_id"] [H,W]; out["surface_depth"] [1,H,W]
     point = fdgs.playback.unproject(cam, torch.tensor([[x, y]]), out["surface_depth"][0, y, x].reshape(1))
+
+`render_contrib` (the same three classes) answers the inverse question -- how much every ROW adds to the image: per row the sum and the
+maximum of its blend weight over the pixels (optionally weighted by a [H,W] image: a lasso, a mask) and the pixels and tiles that show it,
+accumulated over any number of views and times into a `Contribution` (csrc/render.hip: render_contrib_kernel).  `contribution` loops it
+over cameras, `Baked.select_rows` drops what is never seen:
+
+    seen = fdgs.playback.contribution(baked, cameras, pipe, background)       # seen.weight_sum / weight_max / pixels / tiles [N]
+    small = baked.select_rows(seen.keep_mask(min_pixels=1))                   # the same images from those views, fewer bytes
+    inside = baked.render_contrib(cam, pipe, background, pixel_weight=lasso)["contribution"].pixels > 0
 """
 import bisect
 import math
@@ -321,6 +330,122 @@ def unproject(viewpoint_camera, xy, depth, cam_type=None):
         return (pv @ torch.linalg.inv(view))[:, :3]          # (row vectors: p_view = [p_world, 1] @ view, the rasterizer's layout)
 
 
+class Contribution:
+    """Per-row blend weight statistics accumulated over any number of `render_contrib` passes (views, times): ONE zeroed [N,4] int32
+    buffer of fdgs_contrib_row records, `rows`, and views of its columns --
+      weight_sum  float32 [N]  sum over the passes' pixels of v = w * pixel_weight (w = alpha * T, the weight the frame blended the
+                               row's colour with); float32 additions in no fixed order,
+      weight_max  float32 [N]  the largest v of any pixel of any pass (exact),
+      pixels      int32   [N]  pixels with v > 0, summed over the passes (exact),
+      tiles       int32   [N]  16 x 16 tiles holding such a pixel, summed over the passes (exact),
+    and `frames`, the host's count of the passes accumulated.  Rows are in the order of "radii"."""
+
+    def __init__(self, N, device):
+        self.N = int(N)
+        if self.N < 0:
+            raise ValueError("Contribution: N >= 0")
+        self.rows = torch.zeros(self.N, 4, dtype=torch.int32, device=device)
+        self.frames = 0
+
+    @property
+    def device(self):
+        return self.rows.device
+
+    @property
+    def weight_sum(self):
+        return self.rows[:, 0].view(torch.float32)
+
+    @property
+    def weight_max(self):
+        return self.rows[:, 1].view(torch.float32)
+
+    @property
+    def pixels(self):
+        return self.rows[:, 2]
+
+    @property
+    def tiles(self):
+        return self.rows[:, 3]
+
+    def reset(self):
+        self.rows.zero_()
+        self.frames = 0
+
+    def keep_mask(self, min_pixels=1, min_weight_max=0.0, min_weight_sum=0.0):
+        """bool [N]: the rows that reach all three thresholds (pixels >= min_pixels, weight_max >= min_weight_max, weight_sum >=
+        min_weight_sum).  The default keeps what was blended into at least one pixel: the mask `Baked.select_rows` takes."""
+        return (self.pixels >= int(min_pixels)) & (self.weight_max >= float(min_weight_max)) & (self.weight_sum >= float(min_weight_sum))
+
+
+def _render_contrib_state(who, owner, frame_at, sh_degree, device, to_stored, to_model, viewpoint_camera, pipe, bg_color, into, pixel_weight,
+                          scaling_modifier, cam_type, rgb8):
+    """The body of Baked.render_contrib, SparseBaked.render_contrib and Composite.render_contrib: the frame of _render_state, then ONE
+    fdgs_render_contrib over the RasterState it left behind (include/fdgs.h: one more walk over the frame's own sorted lists, which writes
+    nothing into them), accumulated through the owner's stored -> model row map into `into`."""
+    if pipe.compute_cov3D_python or pipe.convert_SHs_python:
+        raise NotImplementedError(f"{who}: pipe.compute_cov3D_python / pipe.convert_SHs_python need the live model; use fdgs.render")
+    with torch.no_grad():
+        raster_settings, frame_time = _renderer._frame_settings(viewpoint_camera, cam_type, bg_color, scaling_modifier, sh_degree, device, pipe)
+        W, H = int(raster_settings.image_width), int(raster_settings.image_height)
+        if into is None:
+            into = Contribution(owner.N, device)
+        elif not isinstance(into, Contribution) or into.N != owner.N or into.device != device:
+            raise ValueError(f"{who}: `into` must be a Contribution of {owner.N} rows on {device}")
+        if pixel_weight is not None:
+            if (not torch.is_tensor(pixel_weight) or pixel_weight.dtype != torch.float32 or pixel_weight.device != device
+                    or tuple(pixel_weight.shape) not in ((H, W), (1, H, W))):
+                raise ValueError(f"{who}: pixel_weight must be a float32 [{H},{W}] or [1,{H},{W}] tensor on {device}")
+            pixel_weight = pixel_weight.detach().contiguous()
+        if owner._pick_row_map is None:          # (stays None for rows stored in the model's order: there is nothing to build)
+            owner._pick_row_map = owner._make_pick_row_map()
+        out, rstate = _state_frame(frame_at(frame_time), raster_settings, to_stored, to_model, None, rgb8)
+        if into.N > 0:
+            _lib.check(_lib.lib().fdgs_render_contrib(_lib.stream_ptr(), rstate.params, _lib.ptr(rstate.geom), _lib.ptr(rstate.binning),
+                                                      _lib.ptr(rstate.img), rstate.capacity, _lib.ptr(pixel_weight),
+                                                      _lib.ptr(owner._pick_row_map), _lib.ptr(into.rows)))
+        into.frames += 1
+        out["contribution"] = into
+        return out
+
+
+_CONTRIB_DOC = """Everything `render(viewpoint_camera, pipe, bg_color, scaling_modifier, cam_type=cam_type, interp=interp, rgb8=rgb8)` returns,
+        bit for bit, plus "contribution": how much every row adds to this image, ACCUMULATED into `into` (a `Contribution` of this
+        object's N rows on its device; None: a new one), at the cost of ONE extra walk over the frame's own sorted lists
+        (fdgs_render_contrib: no second projection, sort or blend).  Per row, over the frame's pixels: the sum and the maximum of
+        v = w * pixel_weight (w = alpha * T, the weight the frame blended the row's colour with), the number of pixels with v > 0 and of
+        the 16 x 16 tiles that hold one.  `pixel_weight`: a float32 [H,W] or [1,H,W] tensor on the device (a lasso, a mask, a saliency
+        map; a pixel whose weight is zero, negative or NaN counts for nothing), None: 1 everywhere.  Rows follow the order of "radii".  A
+        pixel_weight of another shape, dtype or device, or an `into` of another N or device: ValueError."""
+
+
+class _AtTime:
+    """`camera` with another frame time: every other attribute is the camera's own."""
+
+    def __init__(self, camera, time):
+        self._camera, self.time = camera, float(time)
+
+    def __getattr__(self, name):
+        return getattr(self._camera, name)
+
+
+def contribution(obj, cameras, pipe, bg_color, times=None, **kw):
+    """One `Contribution` accumulated over `cameras`: obj.render_contrib (a Baked, SparseBaked or Composite) once per camera at the
+    camera's own time, or, when `times` is given, once per camera and time of `times`.  **kw goes to render_contrib (pixel_weight,
+    scaling_modifier, cam_type, interp; `into` to go on accumulating into an existing one).  The importance statistic of a pruning pass:
+    `baked.select_rows(contribution(baked, cams, pipe, bg).keep_mask())` drops what no view shows."""
+    into = kw.pop("into", None)
+    if into is None:
+        into = Contribution(obj.N, obj.device)
+    for cam in cameras:
+        if times is None:
+            obj.render_contrib(cam, pipe, bg_color, into=into, **kw)
+            continue
+        for t in times:
+            at = {**cam, "time": float(t)} if kw.get("cam_type") == "PanopticSports" else _AtTime(cam, t)
+            obj.render_contrib(at, pipe, bg_color, into=into, **kw)
+    return into
+
+
 class Baked:
     """The deformed, activated state of a model at `times`, resident on the device: positions [N,3], scales [N,3] (exp applied), rotations
     [N,4] (unit quaternions), opacity [N,1] (sigmoid applied), SH [N,16,3] -- what the no-grad branch of render() hands to the rasterizer.
@@ -400,6 +525,56 @@ class Baked:
                                   *self._maps, viewpoint_camera, pipe, bg_color, scaling_modifier, cam_type, alpha_cut, rgb8)
 
     render_pick.__doc__ = _PICK_DOC
+
+    def render_contrib(self, viewpoint_camera, pipe, bg_color, into=None, pixel_weight=None, scaling_modifier=1.0, cam_type=None,
+                       interp="linear", rgb8=None):
+        return _render_contrib_state("Baked.render_contrib", self, lambda t: self.state_at(t, interp)[0], self.active_sh_degree, self.device,
+                                     *self._maps, viewpoint_camera, pipe, bg_color, into, pixel_weight, scaling_modifier, cam_type, rgb8)
+
+    render_contrib.__doc__ = _CONTRIB_DOC
+
+    def select_rows(self, keep):
+        """A new Baked holding only the rows `keep` selects -- a bool mask [N] or an integer index tensor, in the MODEL's row order (the
+        order of "radii", of `Contribution.keep_mask`) --: the same times, head_on and active_sh_degree, arrays of a head that is off
+        stored once, the layout of `bake` (nbytes == bake_bytes(N', T, head_on)).  A snapshot, like `bake`: it shares nothing with
+        this object.  The STORED order is preserved: with `perm`, stored row i is kept iff keep[perm[i]], and the new `perm` maps the
+        kept stored rows to the kept model rows renumbered ascending (new model row k is the k-th kept row of the old model).  Binning
+        breaks depth ties by Gaussian index, so the subset sorts as it did inside the full set: dropping rows with pixels == 0 at a view
+        leaves every pixel of that view's image and depth bit-identical that the frame did not END EARLY.  (The blend ends a pixel at the
+        first entry with T * (1 - alpha) < 1e-4 WITHOUT blending that entry: a row that only ever ends pixels has pixels == 0, and
+        without it such a pixel goes on to the next entry -- a change below the transmittance the pixel had left, < 0.01.  A view in
+        which no pixel saturates is identical as a whole.)  A one-time operation in torch index ops, not a frame.  A mask of another
+        length, or an index outside [0, N): ValueError.  (SparseBaked and Composite have no select_rows: select per model, then bake
+        sparse or compose again.)"""
+        keep = torch.as_tensor(keep, device=self.device)
+        if keep.dtype == torch.bool:
+            if tuple(keep.shape) != (self.N,):
+                raise ValueError(f"Baked.select_rows: a bool mask of {self.N} rows, not {tuple(keep.shape)}")
+            mask = keep
+        else:
+            if keep.dim() != 1 or keep.dtype.is_floating_point or keep.dtype.is_complex:
+                raise ValueError("Baked.select_rows: a bool mask [N] or a 1-D integer index tensor")
+            idx = keep.to(torch.int64)
+            if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self.N):
+                raise ValueError(f"Baked.select_rows: an index outside [0, {self.N})")
+            mask = torch.zeros(self.N, dtype=torch.bool, device=self.device)
+            mask[idx] = True
+        with torch.no_grad():
+            stored_mask = mask if self.perm is None else mask[self.perm.to(torch.int64)]
+            rows = torch.nonzero(stored_mask).reshape(-1)                 # the kept STORED rows, ascending: their order is preserved
+            n, T = int(rows.numel()), len(self.times)
+            perm = None
+            if self.perm is not None:
+                new_id = torch.cumsum(mask.to(torch.int64), 0) - 1          # old model row -> its rank among the kept model rows
+                perm = new_id[self.perm.to(torch.int64)[rows]].to(self.perm.dtype).contiguous()
+            storage = torch.empty(bake_bytes(n, T, self.head_on) // 4, dtype=torch.float32, device=self.device)
+            views = _carve(_field_slots(n, [T if on else 1 for on in self.head_on]), storage)[1]
+            slots = [v if on else v * T for v, on in zip(views, self.head_on)]
+            for h, name in enumerate(FIELDS):
+                for k in range(T if self.head_on[h] else 1):
+                    slots[h][k].copy_(getattr(self.frames[k], name)[rows])
+            frames = [BakedFrame([slots[h][k] for h in range(len(FIELDS))]) for k in range(T)]
+        return Baked(self.times, frames, self.head_on, perm, storage, self.active_sh_degree)
 
 
 def bake(pc, times, max_bytes=None):
@@ -586,6 +761,15 @@ class SparseBaked:
                                   *self._maps, viewpoint_camera, pipe, bg_color, scaling_modifier, cam_type, alpha_cut, rgb8)
 
     render_pick.__doc__ = _PICK_DOC
+
+    def render_contrib(self, viewpoint_camera, pipe, bg_color, into=None, pixel_weight=None, scaling_modifier=1.0, cam_type=None,
+                       interp="linear", rgb8=None):
+        return _render_contrib_state("SparseBaked.render_contrib", self, lambda t: self.state_at(t, interp)[0], self.active_sh_degree,
+                                     self.device, *self._maps, viewpoint_camera, pipe, bg_color, into, pixel_weight, scaling_modifier,
+                                     cam_type, rgb8)
+
+    render_contrib.__doc__ = _CONTRIB_DOC + """
+        (There is no SparseBaked.select_rows: select on the dense bake, or prune the model, and bake sparse again.)"""
 
 
 def bake_sparse(pc, times, tol, max_bytes=None):

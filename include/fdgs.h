@@ -707,6 +707,38 @@ typedef struct fdgs_pick_out {
 int fdgs_render_pick(void* stream, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
                      uint32_t num_rendered, float alpha_cut, const int32_t* row_map_opt, const fdgs_pick_out* out);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Contribution pass (an addition to ABI 6; no existing signature changed): how much every Gaussian adds to a finished frame -- the inverse
+ * of the pick pass's question --, from ONE more walk over the frame's own sorted lists (csrc/render.hip: render_contrib_kernel,
+ * fdgs.playback.Baked.render_contrib).  No second projection, no sort.  The per-Gaussian sum of w = alpha * T is decided inside the
+ * blend and is not linear in a per-Gaussian colour, so this is not a second fdgs_render_fwd but a kernel of its own.
+ *
+ * Valid wherever fdgs_render_pick is valid, with the same geom, binning, img and num_rendered.  Per pixel the tile's list is walked from
+ * the front up to the pixel's n_contrib with exactly the forward's decisions and expressions (the pick pass's walk: w has the bits of
+ * the weight the forward blended the Gaussian's colour with).  v = w, or with a pixel weight v = w * pixel_weight_opt[pixel] as ONE
+ * rounded product.  A pixel or entry with !(v > 0) is skipped entirely -- a zero, negative or NaN weight is neither summed, maxed nor
+ * counted.
+ * -------------------------------------------------------------------------------------------------------- */
+typedef struct fdgs_contrib_row {   /* 16 bytes, one per Gaussian; ACCUMULATED into, never cleared by the call */
+    float    weight_sum;   /* += sum over pixels of v (float32; the order of the additions across tiles is not fixed) */
+    float    weight_max;   /* = max(old, max over pixels of v): exact */
+    uint32_t pixels;       /* += number of pixels with v > 0: exact */
+    uint32_t tiles;        /* += number of 16 x 16 tiles in which at least one pixel had v > 0: exact */
+} fdgs_contrib_row;
+/* rows: device fdgs_contrib_row[P], 16-byte aligned; zero it before the first pass, accumulate any number of frames (views, times) into
+ * it.  Gaussian g goes to rows[row_map_opt ? row_map_opt[g] : g] (row_map_opt: device int32[P] or NULL); an id outside [0, P), before
+ * or after the map, is dropped.  pixel_weight_opt: device float[H*W] or NULL (a lasso, a mask, a saliency map).
+ * FDGS_E_INVALID with a message, before anything is launched, for: a NULL params, geom, binning, img or rows; W or H < 1; P < 0; rows
+ * not 16-byte aligned; pixel_weight_opt or row_map_opt not 4-byte aligned.  P == 0 or num_rendered == 0 succeeds without touching
+ * rows (and without a launch).  Otherwise ONE launch on `stream`, nothing synchronises (params->debug aside); its row in
+ * fdgs_timing_report is "render_contrib".  At most one atomic per word of a record and (tile, list entry): f32 add, u32 max on the
+ * float's bits (valid because v >= +0), u32 add, u32 add of 1.
+ * It WRITES NOTHING into geom, binning or img (the tiles are taken in the order the forward left in img field 4, which is read, not
+ * rebuilt), so a pick, a motion pass or fdgs_raster_bwd of the same frame may follow.  A stale img cannot make it read past a list:
+ * every walk is clamped to the tile's range and num_rendered. */
+int fdgs_render_contrib(void* stream, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
+                        uint32_t num_rendered, const float* pixel_weight_opt, const int32_t* row_map_opt, fdgs_contrib_row* rows);
+
 #ifdef __cplusplus
 }
 #endif
