@@ -28,8 +28,9 @@ import torch
 from . import _lib
 from . import deformation as _deformation
 from . import sh as _sh
-from .playback import (_CONTRIB_DOC, _MOTION_DOC, _PICK_DOC, BakedFrame, SparseBaked, _carve, _checked_interp, _field_mask, _field_slots,
-                       _locate, _perm_maps, _render_contrib_state, _render_motion_state, _render_pick_state, _render_state, _state_arrays)
+from .playback import (_CONTRIB_DOC, _FEATURES_DOC, _MOTION_DOC, _PICK_DOC, BakedFrame, SparseBaked, _carve, _checked_interp, _field_mask,
+                       _field_slots, _locate, _perm_maps, _render_contrib_state, _render_features_state, _render_motion_state, _render_pick_state,
+                       _render_state, _state_arrays)
 
 WRAPS = ("clamp", "loop", "pingpong")
 _SH_ZERO = 1e-13        # entries of a band matrix below this are structural zeros of the rotation (the solve leaves ~1e-16 there)
@@ -312,6 +313,25 @@ class Composite:
     render_contrib.__doc__ = _CONTRIB_DOC + """
         The rows are rows of the whole scene (sum(N), model m's at `slices[m]`; `model_of_rows` splits row indices into (model, row)).
         (There is no Composite.select_rows: select per model with `Baked.select_rows`, then compose again.)"""
+
+    def render_features(self, viewpoint_camera, pipe, bg_color, values, normalize=False, min_alpha=1e-4, scaling_modifier=1.0, cam_type=None,
+                        interp="linear", rgb8=None):
+        return _render_features_state("Composite.render_features", self, lambda t: self.state_at(t, interp), self.active_sh_degree, self.device,
+                                      *self._maps, viewpoint_camera, pipe, bg_color, values, normalize, min_alpha, scaling_modifier, cam_type,
+                                      rgb8)
+
+    render_features.__doc__ = _FEATURES_DOC + """
+        The rows of `values` are rows of the whole scene (sum(N), model m's at `slices[m]`); with `model_indicator()` as the values the
+        features are one matte per placed model, and they sum to "alpha"."""
+
+    def model_indicator(self):
+        """float32 [N, M] on the scene's device, M = len(models): row r holds a 1 in the column of the placed model that owns it (the row
+        ranges `model_of_rows` splits ids by) and zeros elsewhere.  As the `values` of render_features: per-model mattes."""
+        rows = torch.arange(sum(m.N for m in self.models), dtype=torch.int64, device=self.device)
+        model = self.model_of_rows(rows)[0].to(torch.int64)
+        out = torch.zeros(rows.shape[0], len(self.models), dtype=torch.float32, device=self.device)
+        out[rows, model] = 1.0
+        return out
 
     def _make_pick_row_map(self):
         """The stored -> scene row map of fdgs_render_pick: model m's segment is offset_m + perm_m (offset_m + arange for a model stored in

@@ -12,6 +12,8 @@
 // blend weight and the id and depth of the one at which the accumulated alpha reaches a cut; it writes nothing into the frame.
 // Contribution pass (render_contrib_kernel): that walk again, reduced per Gaussian instead of per pixel -- the sum and the maximum of the
 // blend weight over the pixels, the pixels and the tiles that show it --, one atomic record per (tile, entry); it writes nothing into the frame.
+// Feature pass (render_features_kernel): that walk with C per-row channels in place of the colour, sixteen per workgroup and all C in one launch,
+// each with the bits a forward blend of it would give; it writes nothing into the frame.
 // Tile rows are dealt to the XCDs in groups (unit_of_block: workgroup b runs on XCD b % 8), so that neighbouring tiles -- which list
 // the same Gaussians -- share an XCD's 4 MiB L2 and every XCD owns rows from the whole height of the image.
 // Replaces renderCUDA forward/backward of the un-vendored rasterizer (Appendix B.3/B.4).
@@ -405,6 +407,142 @@ __global__ void __launch_bounds__(256) render_pick_kernel(PickArgs a) {
         if (a.pick_weight) a.pick_weight[pix] = best_w;
         if (a.surface_id) a.surface_id[pix] = id_of(s_g);
         if (a.surface_depth) a.surface_depth[pix] = s_depth;
+    }
+}
+
+// ---- the feature pass: C per-row channels blended in one walk ---------------------------------------------------------------------------
+// The pick pass's walk once more (its layout, staging pipeline, tile order, clamps and expressions, compiled without contraction: w has
+// the bits of the forward's w), with per-row VALUES in place of the colour record: channel c of a pixel is the sum over its contributors
+// of values[row, c] * w, accumulated in list order as ONE explicit fused multiply-add per entry -- what the forward's `C0 += Cc.x * w`
+// is compiled to (render_fwd_kernel is built with contraction) --, so a channel has the bits fdgs_render_fwd would blend for it over a zero
+// background, and A = A + w is the pick pass's float32 running sum (the blend of a channel of ones: 1 * w is exact).
+// Channels go in chunks of FEAT_CH = 16, blockIdx.y is the chunk and every chunk re-evaluates w: ONE launch for any C.  The thread that
+// stages entry t also stages that entry's sixteen values (sV[4][256] float4 in LDS, loaded one round ahead with the records); a value whose
+// channel is >= C or whose row is outside [0, rows) is staged as +0, and fma(+0, w, F) leaves F as it is.  In the inner loop every lane reads
+// the same four float4 (broadcast reads).  The chunk size was measured (tools/features_timing.py): 8 keeps the pick pass's
+// occupancy (54 VGPRs, 16.6 KB of LDS) and is faster up to C = 8 (config 4: 0.121 against 0.152 ms at C = 3), 16 (78 VGPRs, 24.8 KB: six
+// waves per SIMD) pays the walk half as often and is faster from C = 9 on (0.161 against 0.215 ms at C = 16, 0.286 against 0.394 at C = 32).
+// recC is not read.  Nothing of the frame is written: no atomics, the planes are the only stores.
+#ifndef FDGS_FEAT_CH
+#define FDGS_FEAT_CH 16                      // (8 at build time is the form it was measured against; a multiple of 4)
+#endif
+constexpr int FEAT_CH = FDGS_FEAT_CH, FEAT_V4 = FEAT_CH / 4;
+static_assert(FEAT_CH % 4 == 0 && FEAT_CH >= 4, "whole float4 records");
+struct FeatArgs : BlendHead {
+    const uint32_t* tile_todo;               // per tile: max n_contrib, the forward's walk length
+    const uint2* ranges; const uint32_t* pair_gid;
+    const float4 *recA, *recB, *recC;
+    const float* bg;
+    const float* final_T; const uint32_t* n_contrib;
+    uint32_t R; int P;                       // what the lists were laid out for: fences for a stale img
+    int empty;                               // 1: no Gaussians or no pairs, every pixel gets +0 and nothing of the frame is read
+    int C; const float* values; int value_stride; int rows;
+    const int32_t* row_map;                  // opt [P]: the row of `values` Gaussian g takes
+    float min_alpha;                         // < 0: raw sums; else F / A where A > min_alpha, 0 elsewhere
+    float* features;                         // [C,H,W]
+    float* alpha;                            // opt [H,W], written by chunk 0
+};
+
+__global__ void __launch_bounds__(256) render_features_kernel(FeatArgs a) {
+#pragma clang fp contract(off)
+    const int tile = a.empty ? unit_of_block(blockIdx.x, a.gx, a.gy, 1, a.bh) : unit_lookup(a.order, a.per_xcd, blockIdx.x, a.gx, a.gy, 1, a.bh);
+    if (tile < 0 || tile >= a.gx * a.gy) return;
+    __shared__ float4 sA[256], sB[256], sV[FEAT_V4][256];
+    const int t = threadIdx.x;
+    const int c0 = (int)blockIdx.y * FEAT_CH;                                // this chunk's first channel
+    const int nch = a.C - c0 < FEAT_CH ? a.C - c0 : FEAT_CH;                 // ... and how many of its sixteen exist (>= 1: the grid)
+    const int x = (tile % a.gx) * TILE + (t & 15), y = (tile / a.gx) * TILE + (t >> 4);
+    const bool inside = x < a.W && y < a.H;
+    const float pxf = (float)x, pyf = (float)y;
+    const size_t pix = (size_t)y * a.W + x, hw = (size_t)a.H * a.W;
+    uint2 range = make_uint2(0u, 0u);
+    uint32_t walk = 0u, own = 0u;
+    if (!a.empty) {
+        range = a.ranges[tile];
+        range.y = range.y < a.R ? range.y : a.R;
+        range.x = range.x < range.y ? range.x : range.y;
+        walk = a.tile_todo[tile];
+        own = inside ? a.n_contrib[pix] : 0u;
+    }
+    const int n_list = (int)(range.y - range.x);
+    const int todo = walk < (uint32_t)n_list ? (int)walk : n_list;           // the tile's walk length, clamped to the list ...
+    const int mine = own < (uint32_t)todo ? (int)own : todo;                // ... and this lane's, clamped to the tile's
+    const int rounds = (todo + 255) / 256;
+    float T = 1.0f, A = 0.0f;
+    float F[FEAT_CH];
+#pragma unroll
+    for (int k = 0; k < FEAT_CH; k++) F[k] = 0.0f;
+    int seen = 0;                            // entries of the list this lane has passed
+    auto gid_of = [&](int r) -> uint32_t {
+        const int e = r * 256 + t;
+        return a.pair_gid[range.x + (e < n_list ? e : n_list - 1)];
+    };
+    // the values of Gaussian g in this chunk: 16-byte loads where the chunk is whole and its address allows them (values itself
+    // is only 4-byte aligned: a row slice of a wider array), else one load per channel that exists
+    auto values_of = [&](uint32_t g, float4 (&v)[FEAT_V4]) {
+#pragma unroll
+        for (int i = 0; i < FEAT_V4; i++) v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (g >= (uint32_t)a.P) return;
+        const uint32_t row = a.row_map ? (uint32_t)a.row_map[g] : g;
+        if (row >= (uint32_t)a.rows) return;                                 // (a -1 of the map is >= rows as well)
+        const float* src = a.values + (size_t)row * (size_t)a.value_stride + c0;
+        if (nch == FEAT_CH && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+#pragma unroll
+            for (int i = 0; i < FEAT_V4; i++) v[i] = reinterpret_cast<const float4*>(src)[i];
+            return;
+        }
+        float q[FEAT_CH];
+#pragma unroll
+        for (int k = 0; k < FEAT_CH; k++) q[k] = k < nch ? src[k] : 0.0f;
+#pragma unroll
+        for (int i = 0; i < FEAT_V4; i++) v[i] = make_float4(q[4 * i], q[4 * i + 1], q[4 * i + 2], q[4 * i + 3]);
+    };
+    uint32_t g_cur = 0u, g_nxt = 0u;
+    float4 rA, rB, rV[FEAT_V4];
+    if (rounds > 0) {
+        g_cur = gid_of(0);
+        if (rounds > 1) g_nxt = gid_of(1);
+        rA = a.recA[g_cur]; rB = a.recB[g_cur]; values_of(g_cur, rV);
+    }
+    for (int r = 0; r < rounds; r++) {
+        if (__syncthreads_count(seen >= mine) == 256) break;
+        sA[t] = rA; sB[t] = rB;
+#pragma unroll
+        for (int i = 0; i < FEAT_V4; i++) sV[i][t] = rV[i];
+        __syncthreads();
+        if (r + 1 < rounds) { g_cur = g_nxt; rA = a.recA[g_cur]; rB = a.recB[g_cur]; values_of(g_cur, rV); }
+        if (r + 2 < rounds) g_nxt = gid_of(r + 2);
+        const int rem = mine - seen;
+        const int lim = rem < 256 ? rem : 256;
+        for (int j = 0; j < lim; j++) {
+            const float4 Aj = sA[j];
+            const float4 B = sB[j];
+            const float dx = Aj.x - pxf, dy = Aj.y - pyf;
+            const float power = blend_power(blend_power_xx(Aj.z, dx), blend_power_xy(Aj.w, dx), B.x, dy);
+            if (power > 0.0f) continue;
+            const float alpha = fminf(FDGS_ALPHA_MAX, B.y * __expf(power));
+            if (alpha < FDGS_ALPHA_MIN) continue;
+            const float w = alpha * T;
+            A = A + w;
+#pragma unroll
+            for (int i = 0; i < FEAT_V4; i++) {
+                const float4 V = sV[i][j];
+                F[4 * i] = __builtin_fmaf(V.x, w, F[4 * i]); F[4 * i + 1] = __builtin_fmaf(V.y, w, F[4 * i + 1]);
+                F[4 * i + 2] = __builtin_fmaf(V.z, w, F[4 * i + 2]); F[4 * i + 3] = __builtin_fmaf(V.w, w, F[4 * i + 3]);
+            }
+            T = T * (1.0f - alpha);
+        }
+        seen += 256;
+    }
+    if (inside) {
+        const bool normalize = a.min_alpha >= 0.0f;
+        const bool ok = A > a.min_alpha;                                     // (a NaN A: false)
+#pragma unroll
+        for (int k = 0; k < FEAT_CH; k++) {
+            const float q = F[k] / A;                                        // (IEEE division, as fdgs_motion_resolve's)
+            if (k < nch) a.features[(size_t)(c0 + k) * hw + pix] = normalize ? (ok ? q : 0.0f) : F[k];
+        }
+        if (a.alpha && blockIdx.y == 0) a.alpha[pix] = A;
     }
 }
 
@@ -1054,6 +1192,37 @@ extern "C" int fdgs_render_pick(void* stream_, const fdgs_raster_params* p, cons
         hipLaunchKernelGGL(render_pick_kernel, dim3(unit_grid(a.gx, a.gy, 1, a.bh)), dim3(256), 0, stream, a);
     }
     FDGS_LAUNCH_CHECK("render_pick", p->debug, stream);
+    return FDGS_OK;
+}
+
+extern "C" int fdgs_render_features(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
+                                    uint32_t R, int C, const float* values, int value_stride, int rows, const int32_t* row_map_opt,
+                                    float min_alpha, float* features, float* alpha_opt) {
+    FDGS_REQUIRE(p && geom && binning && img && values && features, "NULL pointer (params, geom, binning, img, values and features)");
+    FDGS_REQUIRE(p->P >= 0 && p->W >= 1 && p->H >= 1, "bad P/W/H");
+    FDGS_REQUIRE((p->W + TILE - 1) / TILE < 65536 && (p->H + TILE - 1) / TILE < 65536, "image too large");
+    FDGS_REQUIRE(C >= 1 && C <= 8 * 65535, "bad C (1 .. 8 * 65535 channels)");
+    FDGS_REQUIRE(value_stride >= C, "bad value_stride (at least C floats per row)");
+    FDGS_REQUIRE(rows >= 0, "bad rows (negative)");
+    FDGS_REQUIRE(aligned_to(values, 4) && aligned_to(row_map_opt, 4) && aligned_to(features, 4) && aligned_to(alpha_opt, 4),
+                 "arrays must be 4-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    FeatArgs a{};
+    const ImgLayout il = fill_blend_args(a, p, geom, binning, img, R);
+    a.tile_todo = at<uint32_t>(img, il.todo);
+    a.R = R; a.P = p->P;
+    a.empty = (p->P == 0 || R == 0) ? 1 : 0;
+    a.C = C; a.values = values; a.value_stride = value_stride; a.rows = rows; a.row_map = row_map_opt;
+    a.min_alpha = min_alpha >= 0.0f ? min_alpha : -1.0f;                    // (negative or NaN: raw sums)
+    a.features = features; a.alpha = alpha_opt;
+    // the forward's own heaviest-first order, where fdgs_render_fwd wrote one (make_tile_order's condition); never rebuilt here
+    const bool ordered = !a.empty && tiles_ordered(il);
+    a.order = ordered ? at<uint32_t>(img, il.order_f) : nullptr;
+    {
+        FDGS_TIMED("render_features", stream);
+        hipLaunchKernelGGL(render_features_kernel, dim3(unit_grid(a.gx, a.gy, 1, a.bh), (C + FEAT_CH - 1) / FEAT_CH), dim3(256), 0, stream, a);
+    }
+    FDGS_LAUNCH_CHECK("render_features", p->debug, stream);
     return FDGS_OK;
 }
 

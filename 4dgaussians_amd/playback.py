@@ -43,6 +43,13 @@ over cameras, `Baked.select_rows` drops what is never seen:
     seen = fdgs.playback.contribution(baked, cameras, pipe, background)       # seen.weight_sum / weight_max / pixels / tiles [N]
     small = baked.select_rows(seen.keep_mask(min_pixels=1))                   # the same images from those views, fewer bytes
     inside = baked.render_contrib(cam, pipe, background, pixel_weight=lasso)["contribution"].pixels > 0
+
+`render_features` (the same three classes) blends C per-row channels of the caller's -- a per-model indicator, `motion_extent`, a
+`Contribution` column, labels, normals, embeddings -- like a colour, all C in one extra walk over those lists and without touching the
+frame's colours (csrc/render.hip: render_features_kernel):
+
+    out = baked.render_features(cam, pipe, background, seen.weight_sum)       # out["features"] [C,H,W], out["alpha"] [1,H,W]
+    mattes = scene.render_features(cam, pipe, background, scene.model_indicator())["features"]       # one matte per placed model
 """
 import bisect
 import math
@@ -418,6 +425,65 @@ _CONTRIB_DOC = """Everything `render(viewpoint_camera, pipe, bg_color, scaling_m
         pixel_weight of another shape, dtype or device, or an `into` of another N or device: ValueError."""
 
 
+def _checked_values(who, values, N, device):
+    """`values` of render_features as the [N, C] view fdgs_render_features reads in place -> (view, C, floats from one row to the next)."""
+    if (not torch.is_tensor(values) or values.dtype != torch.float32 or values.device != device or values.dim() not in (1, 2)
+            or values.shape[0] != N or (values.dim() == 2 and values.shape[1] < 1)):
+        raise ValueError(f"{who}: values must be a float32 [{N}] or [{N}, C] tensor (C >= 1) on {device}")
+    v = values.detach()
+    if v.dim() == 1:
+        v = v.unsqueeze(1)
+    C = int(v.shape[1])
+    stride = int(v.stride(0)) if N > 1 else C          # (the stride of a dimension of size <= 1 means nothing)
+    if (C > 1 and v.stride(1) != 1) or stride < C:
+        raise ValueError(f"{who}: values must have stride 1 in its last dimension and rows that do not overlap (strides {tuple(values.stride())})")
+    return v, C, stride
+
+
+def _render_features_state(who, owner, frame_at, sh_degree, device, to_stored, to_model, viewpoint_camera, pipe, bg_color, values, normalize,
+                           min_alpha, scaling_modifier, cam_type, rgb8):
+    """The body of Baked.render_features, SparseBaked.render_features and Composite.render_features: the frame of _render_state, then ONE
+    fdgs_render_features over the RasterState it left behind (include/fdgs.h: one more walk over the frame's own sorted lists, which writes
+    nothing into them), reading `values` in place through the owner's stored -> model row map."""
+    if pipe.compute_cov3D_python or pipe.convert_SHs_python:
+        raise NotImplementedError(f"{who}: pipe.compute_cov3D_python / pipe.convert_SHs_python need the live model; use fdgs.render")
+    v, C, stride = _checked_values(who, values, owner.N, device)
+    min_alpha = float(min_alpha)
+    if normalize and not min_alpha >= 0.0:
+        raise ValueError(f"{who}: min_alpha >= 0 with normalize=True, not {min_alpha!r}")
+    with torch.no_grad():
+        raster_settings, frame_time = _renderer._frame_settings(viewpoint_camera, cam_type, bg_color, scaling_modifier, sh_degree, device, pipe)
+        if owner._pick_row_map is None:          # (stays None for rows stored in the model's order: there is nothing to build)
+            owner._pick_row_map = owner._make_pick_row_map()
+        out, rstate = _state_frame(frame_at(frame_time), raster_settings, to_stored, to_model, None, rgb8)
+        p = rstate.params
+        W, H = int(p.W), int(p.H)
+        if owner.N == 0:                          # (an empty tensor has no address to hand over)
+            out["features"], out["alpha"] = torch.zeros(C, H, W, device=device), torch.zeros(1, H, W, device=device)
+            return out
+        features = torch.empty(C, H, W, dtype=torch.float32, device=device)
+        alpha = torch.empty(1, H, W, dtype=torch.float32, device=device)
+        _lib.check(_lib.lib().fdgs_render_features(_lib.stream_ptr(), p, _lib.ptr(rstate.geom), _lib.ptr(rstate.binning), _lib.ptr(rstate.img),
+                                                   rstate.capacity, C, v.data_ptr(), stride, owner.N, _lib.ptr(owner._pick_row_map),
+                                                   min_alpha if normalize else -1.0, _lib.ptr(features), _lib.ptr(alpha)))
+        out["features"], out["alpha"] = features, alpha
+        return out
+
+
+_FEATURES_DOC = """Everything `render(viewpoint_camera, pipe, bg_color, scaling_modifier, cam_type=cam_type, interp=interp, rgb8=rgb8)` returns,
+        bit for bit, plus C per-row channels of the caller's blended like a colour, at the cost of ONE extra walk over the frame's own
+        sorted lists for any C (fdgs_render_features: no second projection, sort or blend; the frame's colours are not touched):
+          "features" float32 [C,H,W]  channel c = the sum over the pixel's contributors of values[row, c] * w, w = alpha * T the weight
+                                      the frame blended the row's colour with: the bits `render(..., bg_color=0, override_color=values[:,
+                                      c:c+3])["render"]` has for that channel.  No background is added.  With normalize=True: that sum
+                                      divided by "alpha" where "alpha" > min_alpha, 0 elsewhere (the expected value of the channel over
+                                      what the pixel shows: a label or an embedding that does not fade at the silhouette),
+          "alpha"    float32 [1,H,W]  the accumulated alpha, the sum of w.
+        `values`: a float32 [N] or [N,C] tensor on the device in the row order of "radii" (a per-model indicator, `motion_extent`, a
+        `Contribution` column, labels, normals, embeddings); read in place -- it need not be contiguous as long as its last dimension
+        has stride 1, e.g. a column slice of a wider array.  Anything else: ValueError."""
+
+
 class _AtTime:
     """`camera` with another frame time: every other attribute is the camera's own."""
 
@@ -532,6 +598,14 @@ class Baked:
                                      *self._maps, viewpoint_camera, pipe, bg_color, into, pixel_weight, scaling_modifier, cam_type, rgb8)
 
     render_contrib.__doc__ = _CONTRIB_DOC
+
+    def render_features(self, viewpoint_camera, pipe, bg_color, values, normalize=False, min_alpha=1e-4, scaling_modifier=1.0, cam_type=None,
+                        interp="linear", rgb8=None):
+        return _render_features_state("Baked.render_features", self, lambda t: self.state_at(t, interp)[0], self.active_sh_degree, self.device,
+                                      *self._maps, viewpoint_camera, pipe, bg_color, values, normalize, min_alpha, scaling_modifier, cam_type,
+                                      rgb8)
+
+    render_features.__doc__ = _FEATURES_DOC
 
     def select_rows(self, keep):
         """A new Baked holding only the rows `keep` selects -- a bool mask [N] or an integer index tensor, in the MODEL's row order (the
@@ -770,6 +844,14 @@ class SparseBaked:
 
     render_contrib.__doc__ = _CONTRIB_DOC + """
         (There is no SparseBaked.select_rows: select on the dense bake, or prune the model, and bake sparse again.)"""
+
+    def render_features(self, viewpoint_camera, pipe, bg_color, values, normalize=False, min_alpha=1e-4, scaling_modifier=1.0, cam_type=None,
+                        interp="linear", rgb8=None):
+        return _render_features_state("SparseBaked.render_features", self, lambda t: self.state_at(t, interp)[0], self.active_sh_degree,
+                                      self.device, *self._maps, viewpoint_camera, pipe, bg_color, values, normalize, min_alpha,
+                                      scaling_modifier, cam_type, rgb8)
+
+    render_features.__doc__ = _FEATURES_DOC
 
 
 def bake_sparse(pc, times, tol, max_bytes=None):

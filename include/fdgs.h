@@ -739,6 +739,40 @@ typedef struct fdgs_contrib_row {   /* 16 bytes, one per Gaussian; ACCUMULATED i
 int fdgs_render_contrib(void* stream, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
                         uint32_t num_rendered, const float* pixel_weight_opt, const int32_t* row_map_opt, fdgs_contrib_row* rows);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Feature pass (an addition to ABI 6; no existing signature changed): C per-row channels of any meaning -- a per-model indicator, a
+ * per-row statistic, a label, a normal, an embedding -- blended into [C,H,W] images by ONE more walk over a finished frame's own sorted
+ * lists (csrc/render.hip: render_features_kernel, fdgs.playback.Baked.render_features).  No second projection, no sort.  The other way
+ * to blend something that is not the model's colour is to overwrite recC of a forward-only frame three channels at a time and call
+ * fdgs_render_fwd again (see fdgs_geom_field): one whole blend per three channels, the frame's colours are gone, and a training frame
+ * does not allow it.  This kernel evaluates alpha, T and w once per (pixel, entry) and chunk of sixteen channels and reads the values
+ * from the caller's own array.
+ *
+ * Valid wherever fdgs_render_pick is valid, with the same geom, binning, img and num_rendered.  Per pixel the tile's list is walked from
+ * the front up to the pixel's n_contrib with exactly the forward's decisions and expressions (the pick pass's walk: w has the bits of
+ * the weight the forward blended the Gaussian's colour with).  Channel c of the pixel is the sum over its contributors, in list order,
+ * of values[row * value_stride + c] * w with row = row_map_opt ? row_map_opt[g] : g, accumulated as ONE fused multiply-add per entry
+ * -- what the forward's colour sums are compiled to --: features[c] has the bits fdgs_render_fwd would write for that channel over a
+ * zero background.  A is the float32 running sum of w in list order (the pick pass's; the blend of a channel of ones).  A Gaussian whose
+ * row is outside [0, rows) -- a -1 of the map included -- blends as zeros.  No background is added.
+ * -------------------------------------------------------------------------------------------------------- */
+/* values: device float, row r at values + r * value_stride, value_stride >= C floats; rows: how many rows it has.  Only 4-byte alignment
+ * is required of it (a row slice [:, a:a+C] of a wider array is legal); 16-byte loads are used where an address allows them.
+ * row_map_opt: device int32[P] or NULL.  features: device float[C*H*W], plane c at features + c * H * W.  alpha_opt: device float[H*W]
+ * or NULL, = A.  min_alpha < 0 or NaN: features holds the raw sums.  min_alpha >= 0: features[c] = sum / A (IEEE division, as
+ * fdgs_motion_resolve's) where A > min_alpha and +0 elsewhere (a NaN A gives +0); alpha_opt is A either way.
+ * FDGS_E_INVALID with a message, before anything is launched, for: a NULL params, geom, binning, img, values or features; W or H < 1;
+ * C < 1 or C > 8 * 65535; value_stride < C; rows < 0; values, row_map_opt, features or alpha_opt not 4-byte aligned.  P == 0 or
+ * num_rendered == 0 succeeds and writes +0 everywhere, without reading the frame.  ONE launch on `stream` for any C (the channels go in
+ * chunks of sixteen, one workgroup per tile and chunk), nothing synchronises (params->debug aside); its row in fdgs_timing_report is
+ * "render_features".
+ * It WRITES NOTHING into the frame -- geom, binning and img keep their bits, no atomics; the tiles are taken in the order the forward left
+ * in img field 4, which is read, not rebuilt --, so a pick, contribution or motion pass, or fdgs_raster_bwd, may follow.  A stale img
+ * cannot make it read past a list: every walk is clamped to the tile's range, the tile's walk length and num_rendered. */
+int fdgs_render_features(void* stream, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
+                         uint32_t num_rendered, int C, const float* values, int value_stride, int rows,
+                         const int32_t* row_map_opt, float min_alpha, float* features /* [C,H,W] */, float* alpha_opt /* [H,W] */);
+
 #ifdef __cplusplus
 }
 #endif
