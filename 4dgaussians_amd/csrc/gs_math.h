@@ -1,5 +1,6 @@
 // gs_math.h -- per-Gaussian projection arithmetic (forward and backward) of the HIP kernels in preprocess.hip (written host / device
-// neutral: plain inline functions; checked stage by stage against the oracle through the kernels, tests/test_gpu_raster.py).
+// neutral: plain inline functions; checked stage by stage against the oracle through the kernels, tests/test_gpu_raster.py, and on the
+// CPU through the host twins fdgs_preprocess_host / fdgs_preprocess_bwd_host of preprocess.hip, tests/test_preprocess_host.py).
 //
 // Arithmetic follows SURVEY.md Appendix B.1 / B.5 (the un-vendored rasterizer the reference calls at
 // gaussian_renderer/__init__.py:120-128); the in-tree formulas it must agree with are
@@ -301,6 +302,11 @@ FDGS_HD void sh_bwd(int deg, const float* sh, const float* p, const float* campo
     }
     float dot = x * ddx + y * ddy + z * ddz;
     dmean[0] += (ddx - x * dot) / len; dmean[1] += (ddy - y * dot) / len; dmean[2] += (ddz - z * dot) / len;
+}
+
+// d L / d (pixel position) -> d L / d (NDC position): d pix / d ndc = W/2, H/2 (ndc2pix)
+FDGS_HD void mean2d_grad_to_ndc(float gx_pix, float gy_pix, int W, int H, float* g_ndc) {
+    g_ndc[0] = gx_pix * 0.5f * (float)W; g_ndc[1] = gy_pix * 0.5f * (float)H;
 }
 
 // conic / depth / mean2D gradients -> dmean (+=), dcov6 (written)

@@ -10,9 +10,9 @@
 
 namespace fdgs {
 
-__device__ __forceinline__ void load_cam(CamConst& c, const float* __restrict__ view, const float* __restrict__ proj,
-                                         const float* __restrict__ campos, int W, int H, float tanfovx, float tanfovy,
-                                         float scale_mod, int D, int M) {
+FDGS_HD void load_cam(CamConst& c, const float* __restrict__ view, const float* __restrict__ proj,
+                      const float* __restrict__ campos, int W, int H, float tanfovx, float tanfovy,
+                      float scale_mod, int D, int M) {
 #pragma unroll
     for (int i = 0; i < 16; i++) { c.view[i] = view[i]; c.proj[i] = proj[i]; }
     if (campos) { c.campos[0] = campos[0]; c.campos[1] = campos[1]; c.campos[2] = campos[2]; }
@@ -294,7 +294,7 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(PreBwdArgs a) {
 #pragma unroll
         for (int k = 0; k < 6; k++) c6[k] = a.cov3D[6 * (size_t)i + k];
         // mean2D gradient is handed back in NDC units (d pix / d ndc = W/2, H/2), like the reference's viewspace grad
-        m2d[0] = g0.x * 0.5f * (float)a.W; m2d[1] = g0.y * 0.5f * (float)a.H;
+        mean2d_grad_to_ndc(g0.x, g0.y, a.W, a.H, m2d);
         dop = g1.y;
         drgb[0] = g1.z; drgb[1] = g1.w; drgb[2] = g2.x;
         float dconic[3] = {g0.z, g0.w, g1.x};
@@ -589,5 +589,85 @@ extern "C" int fdgs_mark_visible(void* stream_, int P, const float* means3D, con
     hipStream_t stream = (hipStream_t)stream_;
     { FDGS_TIMED("mark_visible", stream); hipLaunchKernelGGL(mark_visible_kernel, dim3(cdiv(P, 256)), dim3(256), 0, stream, P, means3D, viewmatrix, present); }
     FDGS_LAUNCH_CHECK("mark_visible", 0, stream);
+    return FDGS_OK;
+}
+
+// ---- host twins of the two projection kernels (include/fdgs.h: fdgs_preprocess_host, fdgs_preprocess_bwd_host) -------------------------
+// A loop over the Gaussians on the CPU around the functions of gs_math.h the kernels above call, in the kernels' order, with host pointers.
+// No arithmetic of their own: what they return is what gs_math.h computes (host rounding: no contraction, the kernels may fuse).
+
+extern "C" int fdgs_preprocess_host(const fdgs_raster_params* p, int32_t* radii, float* xy, float* conic, float* depth, float* rgb,
+                                    uint32_t* clamped, float* cov3D, uint32_t* rect, uint32_t* tiles) {
+    int rc = validate_raster_params(p);
+    if (rc) return rc;
+    FDGS_REQUIRE(p->P == 0 || (radii && xy && conic && depth && rgb && clamped && cov3D && rect && tiles), "an output array is NULL");
+    CamConst c;
+    load_cam(c, p->viewmatrix, p->projmatrix, p->campos, p->W, p->H, p->tanfovx, p->tanfovy, p->scale_modifier, p->sh_degree, p->sh_coeffs);
+    for (size_t i = 0; i < (size_t)p->P; i++) {
+        const float* pos = p->means3D + 3 * i;
+        float c6[6];
+        if (p->cov3D_precomp) {
+            for (int k = 0; k < 6; k++) c6[k] = p->cov3D_precomp[6 * i + k];
+        } else {
+            cov3d_from_scale_rot(p->scales + 3 * i, c.scale_mod, p->rotations + 4 * i, c6);
+        }
+        radii[i] = 0; tiles[i] = 0; clamped[i] = 0; depth[i] = 0.f;
+        xy[2 * i] = xy[2 * i + 1] = 0.f; rect[2 * i] = rect[2 * i + 1] = 0u;
+        for (int k = 0; k < 3; k++) { conic[3 * i + k] = 0.f; rgb[3 * i + k] = 0.f; }
+        for (int k = 0; k < 6; k++) cov3D[6 * i + k] = 0.f;
+        GeoOut g;
+        if (!project_gaussian(c, pos, c6, &g)) continue;
+        if (p->colors_precomp) {
+            for (int k = 0; k < 3; k++) rgb[3 * i + k] = p->colors_precomp[3 * i + k];
+        } else {
+            clamped[i] = sh_to_rgb(c.D, p->shs + i * (size_t)c.M * 3, pos, c.campos, rgb + 3 * i);
+        }
+        radii[i] = g.radius; tiles[i] = (uint32_t)g.tiles; depth[i] = g.depth;
+        xy[2 * i] = g.px; xy[2 * i + 1] = g.py;
+        rect[2 * i] = g.rect_min; rect[2 * i + 1] = g.rect_max;
+        for (int k = 0; k < 3; k++) conic[3 * i + k] = g.conic[k];
+        for (int k = 0; k < 6; k++) cov3D[6 * i + k] = c6[k];
+    }
+    return FDGS_OK;
+}
+
+extern "C" int fdgs_preprocess_bwd_host(const fdgs_raster_params* p, const uint32_t* tiles, const uint32_t* clamped, const float* cov3D,
+                                        const float* d_xy, const float* d_conic, const float* d_rgb, const float* d_depth,
+                                        float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
+                                        float* dL_dcov3D) {
+    int rc = validate_raster_params(p);
+    if (rc) return rc;
+    const bool has_cov = p->cov3D_precomp != nullptr;
+    FDGS_REQUIRE(p->P == 0 || (tiles && cov3D && d_xy && d_conic && d_rgb && dL_dmeans2D && dL_dmeans3D && dL_dcov3D), "an array is NULL");
+    FDGS_REQUIRE(p->P == 0 || !p->shs || (clamped && dL_dsh), "SH inputs need clamped and dL_dsh");
+    FDGS_REQUIRE(p->P == 0 || has_cov || (dL_dscales && dL_drotations), "scale/rotation inputs need dL_dscales and dL_drotations");
+    CamConst c;
+    load_cam(c, p->viewmatrix, p->projmatrix, p->campos, p->W, p->H, p->tanfovx, p->tanfovy, p->scale_modifier, p->sh_degree, p->sh_coeffs);
+    const int M = p->sh_coeffs;
+    for (size_t i = 0; i < (size_t)p->P; i++) {
+        float m2d[3] = {0.f, 0.f, 0.f}, dcov6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float dmean[3] = {0.f, 0.f, 0.f}, ds[3] = {0.f, 0.f, 0.f}, dq[4] = {0.f, 0.f, 0.f, 0.f};
+        float dsh[48];
+        for (int k = 0; k < 48; k++) dsh[k] = 0.f;
+        const float dd = d_depth ? d_depth[i] : 0.f;
+        const float* gxy = d_xy + 2 * i; const float* gco = d_conic + 3 * i; const float* grgb = d_rgb + 3 * i;
+        // (the kernel's rule: a Gaussian without tiles, or with an all-zero line from the blending backward, writes zero rows)
+        const bool any_grad = gxy[0] != 0.f || gxy[1] != 0.f || gco[0] != 0.f || gco[1] != 0.f || gco[2] != 0.f || grgb[0] != 0.f ||
+                              grgb[1] != 0.f || grgb[2] != 0.f || dd != 0.f;
+        if (tiles[i] != 0 && any_grad) {
+            const float* pos = p->means3D + 3 * i;
+            mean2d_grad_to_ndc(gxy[0], gxy[1], p->W, p->H, m2d);
+            project_bwd(c, pos, cov3D + 6 * i, gco, dd, m2d[0], m2d[1], dmean, dcov6);
+            if (p->shs) sh_bwd(c.D, p->shs + i * (size_t)M * 3, pos, c.campos, clamped[i], grgb, dsh, dmean);
+            if (!has_cov) cov3d_bwd(p->scales + 3 * i, c.scale_mod, p->rotations + 4 * i, dcov6, ds, dq);
+        }
+        for (int k = 0; k < 3; k++) { dL_dmeans2D[3 * i + k] = m2d[k]; dL_dmeans3D[3 * i + k] = dmean[k]; }
+        for (int k = 0; k < 6; k++) dL_dcov3D[6 * i + k] = dcov6[k];
+        if (p->shs) for (int k = 0; k < M * 3; k++) dL_dsh[i * (size_t)M * 3 + k] = dsh[k];
+        if (!has_cov) {
+            for (int k = 0; k < 3; k++) dL_dscales[3 * i + k] = ds[k];
+            for (int k = 0; k < 4; k++) dL_drotations[4 * i + k] = dq[k];
+        }
+    }
     return FDGS_OK;
 }

@@ -202,6 +202,26 @@ int fdgs_raster_bwd(void* stream, const fdgs_raster_params* p, const void* geom,
 int fdgs_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                       uint8_t* present);
 
+/* Host twins of the two per-Gaussian projection kernels (stage 1 and the chain-rule half of fdgs_raster_bwd): a loop over the Gaussians on
+ * the CPU around the very functions of csrc/gs_math.h the kernels call, so the projection arithmetic can be checked without a GPU.  Every
+ * pointer -- those inside `p` included -- is a HOST pointer.  `p` is validated as for fdgs_preprocess_fwd, so bg must be non-NULL (and campos
+ * with SH inputs) although the values of bg, opacities, visibility and acc_zero are never read.  Not bit for bit the
+ * device's result: the kernels may contract a * b + c, the host build does not.
+ *   fdgs_preprocess_host: per Gaussian radii[P], xy[P,2] (pixels), conic[P,3] (xx, xy, yy), depth[P], rgb[P,3], clamped[P] (bit c = channel c
+ *     was clamped at 0), cov3D[P,6], rect[P,2] (xmin|ymin<<16, xmax|ymax<<16) and tiles[P] = tiles of the 3-sigma square (what the kernel
+ *     counts without exact tile culling).  A culled Gaussian gets zeros everywhere.
+ *   fdgs_preprocess_bwd_host: tiles / clamped / cov3D as the forward twin left them; the per-Gaussian sums the blending backward leaves in
+ *     fdgs_raster_grads::scratch_acc as separate arrays: d_xy[P,2] = dL/d(xy) in pixel units, d_conic[P,3] = dL/d(conic) with the kernel's
+ *     half-weight xy entry, d_rgb[P,3], d_depth[P] (NULL: zeros).  Outputs as fdgs_raster_grads: dL_dmeans2D[P,3] (NDC units, z = 0),
+ *     dL_dmeans3D[P,3], dL_dsh[P,M,3] (with shs), dL_dscales[P,3] / dL_drotations[P,4] (with scales and rotations), dL_dcov3D[P,6].  A
+ *     Gaussian without tiles gets zero rows, as from the kernel. */
+int fdgs_preprocess_host(const fdgs_raster_params* p, int32_t* radii, float* xy, float* conic, float* depth, float* rgb,
+                         uint32_t* clamped, float* cov3D, uint32_t* rect, uint32_t* tiles);
+int fdgs_preprocess_bwd_host(const fdgs_raster_params* p, const uint32_t* tiles, const uint32_t* clamped, const float* cov3D,
+                             const float* d_xy, const float* d_conic, const float* d_rgb, const float* d_depth,
+                             float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
+                             float* dL_dcov3D);
+
 /* Test/diagnostic access to geom fields (device pointers into `geom`):
  * 0 depth f32[P]; 1 recA float4[P] (x,y,conic.xx,conic.xy); 2 recB float4[P] (conic.yy,opacity,depth,0);
  * 3 recC float4[P] (r,g,b,0); 4 cov3D f32[P,6]; 5 tiles_touched u32[P]; 6 clamped u32[P] (bit c = channel c);

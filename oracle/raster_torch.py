@@ -72,11 +72,11 @@ def sh_to_rgb(deg, sh, dirs):
     return res
 
 
-def rasterize(*, means3D, opacities, viewmatrix, projmatrix, campos, bg, image_height, image_width, tanfovx, tanfovy,
-              sh_degree=0, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
-              scale_modifier=1.0, means2D=None):
-    """Returns (color [3,H,W], depth [1,H,W], radii [P] int32). `means2D` ([P,3], optional) is the reference's
-    gradient sink: its x,y are added (as zeros) in NDC units so that means2D.grad is d L / d ndc."""
+def project(*, means3D, viewmatrix, projmatrix, campos, image_height, image_width, tanfovx, tanfovy, sh_degree=0, shs=None,
+            colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, scale_modifier=1.0, means2D=None):
+    """The per-Gaussian part of `rasterize` (Appendix B.1; gradient conventions of B.5 as in the module docstring): a dict of
+    px, py [P] (pixel position), conic (three [P] tensors xx, xy, yy), tz [P] (view depth), rgb [P,3], Sigma [P,3,3] (the 3D covariance),
+    radii [P] int32, rect (rx0, ry0, rx1, ry1: int64 [P] each) and vis [P] bool."""
     dt, dev = means3D.dtype, means3D.device
     H, W = int(image_height), int(image_width)
     P = means3D.shape[0]
@@ -143,6 +143,21 @@ def rasterize(*, means3D, opacities, viewmatrix, projmatrix, campos, bg, image_h
         rgb = torch.clamp_min(sh_to_rgb(sh_degree, shs.reshape(P, -1, 3), d) + 0.5, 0.0)
     else:
         rgb = colors_precomp
+    return dict(px=px, py=py, conic=(conx, cony, conz), tz=tz, rgb=rgb, Sigma=Sigma, radii=radii, rect=(rx0, ry0, rx1, ry1), vis=vis)
+
+
+def rasterize(*, means3D, opacities, viewmatrix, projmatrix, campos, bg, image_height, image_width, tanfovx, tanfovy,
+              sh_degree=0, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
+              scale_modifier=1.0, means2D=None):
+    """Returns (color [3,H,W], depth [1,H,W], radii [P] int32). `means2D` ([P,3], optional) is the reference's
+    gradient sink: its x,y are added (as zeros) in NDC units so that means2D.grad is d L / d ndc."""
+    dt, dev = means3D.dtype, means3D.device
+    H, W = int(image_height), int(image_width)
+    g = project(means3D=means3D, viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos, image_height=H, image_width=W,
+                tanfovx=tanfovx, tanfovy=tanfovy, sh_degree=sh_degree, shs=shs, colors_precomp=colors_precomp, scales=scales,
+                rotations=rotations, cov3D_precomp=cov3D_precomp, scale_modifier=scale_modifier, means2D=means2D)
+    px, py, (conx, cony, conz), tz, rgb, radii, (rx0, ry0, rx1, ry1), vis = (g["px"], g["py"], g["conic"], g["tz"], g["rgb"], g["radii"],
+                                                                             g["rect"], g["vis"])
     # depth order (stable; ties by index like the radix sort on (tile|depth) keys)
     idx = torch.nonzero(vis).squeeze(1)
     order = torch.sort(tz[idx].detach(), stable=True).indices

@@ -24,6 +24,10 @@ def raster_scene(n, width, height, seed=0, theta=30.0, sh_degree=3, scale_boost=
                 tanfovx=math.tan(cam.FoVx * 0.5), tanfovy=math.tan(cam.FoVy * 0.5), sh_degree=sh_degree)
 
 
+# (SH coefficients stored per row, active degree): every pair the settings tests of the rasterizer and of its host twin run
+SH_PAIRS = [(16, 2), (16, 0), (12, 2), (9, 2), (9, 1), (4, 1), (1, 0)]
+
+
 def rel_l2(a, b):
     a, b = np.asarray(a, np.float64).ravel(), np.asarray(b, np.float64).ravel()
     d = np.linalg.norm(b)

@@ -335,13 +335,14 @@ def test_module_api_matches_reference_signature_and_scalar_time():
     assert torch.equal(a[3], gi[3]) and torch.equal(a[4], gi[4])
 
 
-@pytest.mark.parametrize("cfg,stage", [("dynerf_default", "fine"), ("dnerf_bouncingballs", "fine"), ("dynerf_default", "coarse")])
-def test_render_end_to_end_vs_oracle(cfg, stage):
-    """render() (deform -> activations -> rasterize) against oracle deform -> oracle rasterizer, image and every gradient."""
+def _render_end_to_end_vs_oracle(cfg, stage, active_sh_degree=3, scaling_modifier=1.0, bg=(0.0, 0.0, 0.0)):
+    """render() (deform -> activations -> rasterize) against oracle deform -> oracle rasterizer, image and every gradient, at the model's
+    active SH degree, a scale modifier and a background colour."""
     dev = torch.device("cuda:0")
     fd = _fdgs()
     n, W, H = 4000, 200, 152
     pc = synthetic.SynthModel(n, cfg, seed=21)
+    pc.active_sh_degree = active_sh_degree
     cam = synthetic.make_camera(W, H, theta_deg=40.0, time=0.6)
     with torch.no_grad():
         pc._scaling.add_(1.0)  # bigger splats so that most pixels are covered
@@ -359,8 +360,9 @@ def test_render_end_to_end_vs_oracle(cfg, stage):
         rot = torch.nn.functional.normalize(leaves["_rotation"])
     f = lambda x: np.ascontiguousarray(x.detach().numpy())
     o = RasterOracle(means3D=f(m3), scales=f(sc), rotations=f(rot), opacities=f(op), shs=f(sh), viewmatrix=f(cam.world_view_transform),
-                     projmatrix=f(cam.full_proj_transform), campos=f(cam.camera_center), bg=np.zeros(3, np.float32), image_height=H,
-                     image_width=W, tanfovx=math.tan(cam.FoVx * 0.5), tanfovy=math.tan(cam.FoVy * 0.5), sh_degree=3)
+                     projmatrix=f(cam.full_proj_transform), campos=f(cam.camera_center), bg=np.array(bg, np.float32), image_height=H,
+                     image_width=W, tanfovx=math.tan(cam.FoVx * 0.5), tanfovy=math.tan(cam.FoVy * 0.5), sh_degree=active_sh_degree,
+                     scale_modifier=scaling_modifier)
     target = np.random.default_rng(0).random(o.color.shape).astype(np.float32)
     dc = (np.sign(o.color - target) / o.color.size).astype(np.float32)
     go = o.backward(dc)
@@ -373,11 +375,13 @@ def test_render_end_to_end_vs_oracle(cfg, stage):
     g_ref = torch.autograd.grad(outs, wanted, grad_outputs=gouts, allow_unused=True)
 
     pc = pc.to(dev)
-    res = fd.render(cam.to(dev), pc, synthetic.PipelineParams(), torch.zeros(3, device=dev), stage=stage)
+    pc.active_sh_degree = active_sh_degree
+    res = fd.render(cam.to(dev), pc, synthetic.PipelineParams(), torch.tensor(bg, dtype=torch.float32, device=dev), scaling_modifier=scaling_modifier,
+                    stage=stage)
     img = res["render"]
     d = np.abs(img.detach().cpu().numpy() - o.color)
     psnr = 10 * math.log10(1.0 / max(float((d ** 2).mean()), 1e-20))
-    print(f"[render {cfg} {stage}] max|dC|={d.max():.2e} mean={d.mean():.2e} psnr={psnr:.1f} dB, visible={(o.radii > 0).sum()}")
+    print(f"[render {cfg} {stage} deg={active_sh_degree} mod={scaling_modifier}] max|dC|={d.max():.2e} mean={d.mean():.2e} psnr={psnr:.1f} dB, visible={(o.radii > 0).sum()}")
     assert d.mean() < 5e-6 and psnr > 75.0
     assert res["depth"].shape == (1, H, W) and res["radii"].shape == (n,) and res["visibility_filter"].dtype == torch.bool
     (img * torch.tensor(dc, device=dev)).sum().backward()
@@ -395,6 +399,24 @@ def test_render_end_to_end_vs_oracle(cfg, stage):
     for k, v in rep.items():
         assert v < 1e-3, (k, v)
     assert rel_l2(res["viewspace_points"].grad.cpu().numpy(), go["means2D"]) < 1e-3
+    return gp
+
+
+@pytest.mark.parametrize("cfg,stage", [("dynerf_default", "fine"), ("dnerf_bouncingballs", "fine"), ("dynerf_default", "coarse")])
+def test_render_end_to_end_vs_oracle(cfg, stage):
+    _render_end_to_end_vs_oracle(cfg, stage)
+
+
+@pytest.mark.parametrize("stage,active_sh_degree,scaling_modifier", [("fine", 0, 1.0), ("fine", 1, 1.0), ("fine", 2, 1.0), ("fine", 2, 0.7), ("fine", 3, 0.7),
+                                                                     ("coarse", 2, 0.7)])
+def test_render_end_to_end_lower_sh_degrees_and_scale_modifier(stage, active_sh_degree, scaling_modifier):
+    """The same model, camera and bounds at the SH degrees training passes through (the fused deformation epilogue of the projection backward in
+    the fine stage), with a scale modifier and a background whose channels differ.  Coarse stage: the SH bands above the active degree receive
+    exactly no gradient."""
+    gp = _render_end_to_end_vs_oracle("dynerf_default", stage, active_sh_degree, scaling_modifier, bg=(0.9, 0.1, 0.4))
+    if stage == "coarse":
+        g = gp["_features_rest"].grad
+        assert g is not None and g.shape[1] == 15 and not bool(g[:, (active_sh_degree + 1) ** 2 - 1:].any())
 
 
 # ---- plane gradients on the matrix cores (D4 splat) -------------------------------------------------------------------

@@ -18,11 +18,11 @@ def _mod():
     return importlib.import_module("4dgaussians_amd")
 
 
-def _settings(sc, dev, debug=True):
+def _settings(sc, dev, debug=True, scale_modifier=1.0):
     R = _mod().rasterizer
     return R.GaussianRasterizationSettings(
         image_height=sc["image_height"], image_width=sc["image_width"], tanfovx=sc["tanfovx"], tanfovy=sc["tanfovy"],
-        bg=torch.tensor(sc["bg"], device=dev), scale_modifier=1.0, viewmatrix=torch.tensor(sc["viewmatrix"], device=dev),
+        bg=torch.tensor(sc["bg"], device=dev), scale_modifier=scale_modifier, viewmatrix=torch.tensor(sc["viewmatrix"], device=dev),
         projmatrix=torch.tensor(sc["projmatrix"], device=dev), sh_degree=sc["sh_degree"],
         campos=torch.tensor(sc["campos"], device=dev), prefiltered=False, debug=debug)
 
@@ -105,8 +105,9 @@ def _radii_mismatches_sit_on_a_ceil_boundary(sc, radii, o):
     if len(rows) == 0:
         return
     sub = dict(sc)
-    for k in ("means3D", "shs", "opacities", "scales", "rotations"):
-        sub[k] = sc[k][rows]
+    for k in ("means3D", "shs", "colors_precomp", "opacities", "scales", "rotations", "cov3D_precomp"):
+        if sub.get(k) is not None:
+            sub[k] = sc[k][rows]
     pre = RasterOracle(**sub, dtype=np.float64).field("radius_pre")
     dist = np.abs(pre - np.rint(pre)) / np.maximum(pre, 1e-30)
     for r, d, v in zip(rows, dist, pre):

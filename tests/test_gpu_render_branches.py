@@ -212,11 +212,17 @@ def test_hip_preprocess_cov3d_and_sh_colour_match_reference_python():
             np.testing.assert_allclose(out[3][vis, :3], Z[f"sh.colors.deg{deg}"][vis], rtol=0, atol=2e-6)
 
 
-@pytest.mark.parametrize("cfg", ["dynerf_default", "dnerf_bouncingballs"])
-def test_fused_backward_node_equals_two_node_form(cfg, monkeypatch):
+# (active SH degree, scale modifier): the model's full degree without a modifier, a degree training passes through, degree 0 with a modifier
+_DEG_MOD = [(3, 1.0), (2, 1.0), (0, 0.7)]
+
+
+@pytest.mark.parametrize("cfg,active_sh_degree,scaling_modifier", [(c, d, m) for c in ("dynerf_default", "dnerf_bouncingballs") for d, m in _DEG_MOD],
+                         ids=[c if (d, m) == (3, 1.0) else f"{c}-deg{d}-mod{m}" for c in ("dynerf_default", "dnerf_bouncingballs") for d, m in _DEG_MOD])
+def test_fused_backward_node_equals_two_node_form(cfg, active_sh_degree, scaling_modifier, monkeypatch):
     """render()'s fine stage as ONE autograd node (rasterizer backward writing straight into the deformation backward's packed rows,
     fdgs_raster_deform_epilogue) against the two-node form (five gradient tensors through autograd + the packing kernel): same
-    image bit for bit, every gradient equal to summation noise; also with a gradient on the depth image and under no_grad."""
+    image bit for bit, every gradient equal to summation noise; also with a gradient on the depth image and under no_grad -- at the
+    model's full SH degree and below it, without and with a scale modifier."""
     fd = _fd()
     dev = torch.device("cuda:0")
     cam = synthetic.make_camera(240, 180, theta_deg=-35.0, time=0.45).to(dev)
@@ -227,24 +233,27 @@ def test_fused_backward_node_equals_two_node_form(cfg, monkeypatch):
     for fused in (True, False):
         monkeypatch.setattr(fd.renderer, "FUSED_BACKWARD", fused)
         pc = _model(7001, cfg, seed=23)           # (odd count: the last 128-row block of the packed rows is partly padding)
-        res = fd.render(cam, pc, _Pipe(), torch.zeros(3, device=dev), stage="fine")
+        pc.active_sh_degree = active_sh_degree
+        res = fd.render(cam, pc, _Pipe(), torch.zeros(3, device=dev), scaling_modifier=scaling_modifier, stage="fine")
         ((res["render"] * w).sum() + (res["depth"] * wd).sum()).backward()
         out.append((res, {k: p.grad.clone() for k, p in pc.named_parameters() if p.grad is not None}, res["viewspace_points"].grad.clone()))
         with torch.no_grad():
-            r2 = fd.render(cam, pc, _Pipe(), torch.zeros(3, device=dev), stage="fine")
+            r2 = fd.render(cam, pc, _Pipe(), torch.zeros(3, device=dev), scaling_modifier=scaling_modifier, stage="fine")
         assert torch.equal(r2["render"], res["render"]) and r2["render"].grad_fn is None
     (ra, ga, va), (rb, gb, vb) = out
     assert torch.equal(ra["render"], rb["render"]) and torch.equal(ra["depth"], rb["depth"]) and torch.equal(ra["radii"], rb["radii"])
     assert set(ga) == set(gb)
     worst = max((rel_l2(ga[k].cpu().numpy(), gb[k].cpu().numpy()), k) for k in ga)
-    print(f"[{cfg}] fused vs two-node: worst gradient rel-L2 {worst[0]:.1e} ({worst[1]})")
+    print(f"[{cfg} deg={active_sh_degree} mod={scaling_modifier}] fused vs two-node: worst gradient rel-L2 {worst[0]:.1e} ({worst[1]})")
     assert worst[0] < 2e-5
     assert rel_l2(va.cpu().numpy(), vb.cpu().numpy()) < 1e-6
 
 
-@pytest.mark.parametrize("n", [2, 70, 129, 1000])   # (one point alone makes the bounding-box aabb degenerate: 0/0 in any implementation)
+# (one point alone makes the bounding-box aabb degenerate: 0/0 in any implementation); 129 also at SH degree 1 with a scale modifier
+@pytest.mark.parametrize("n,active_sh_degree,scaling_modifier", [(2, 3, 1.0), (70, 3, 1.0), (129, 3, 1.0), (129, 1, 0.7), (1000, 3, 1.0)],
+                         ids=["2", "70", "129", "129-deg1-mod0.7", "1000"])
 @pytest.mark.parametrize("assign", [True, False])
-def test_fused_backward_small_and_ragged_counts_both_epilogue_modes(n, assign, monkeypatch):
+def test_fused_backward_small_and_ragged_counts_both_epilogue_modes(n, active_sh_degree, scaling_modifier, assign, monkeypatch):
     """Gaussian counts that do not fill a 64-row wave block / a 128-row padded block, and both modes of the rasterizer backward's
     deformation epilogue (assign into an uninitialised arena / accumulate into a zero-filled one), against the two-node form."""
     fd = _fd()
@@ -256,10 +265,11 @@ def test_fused_backward_small_and_ragged_counts_both_epilogue_modes(n, assign, m
         monkeypatch.setattr(fd.renderer, "FUSED_BACKWARD", fused)
         monkeypatch.setattr(fd.renderer, "EPILOGUE_ASSIGN", assign)
         pc = _model(n, "dynerf_default", seed=31, boost=2.5)
+        pc.active_sh_degree = active_sh_degree
         # poison the caching allocator's free blocks: an "assign" epilogue that forgot a row would hand back garbage, not zeros
         junk = torch.full((4_000_000,), float("nan"), device=dev)
         del junk
-        res = fd.render(cam, pc, _Pipe(), torch.zeros(3, device=dev), stage="fine")
+        res = fd.render(cam, pc, _Pipe(), torch.zeros(3, device=dev), scaling_modifier=scaling_modifier, stage="fine")
         (res["render"] * w).sum().backward()
         grads.append({k: p.grad.clone() for k, p in pc.named_parameters() if p.grad is not None})
     a, b = grads
