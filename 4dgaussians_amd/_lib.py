@@ -198,6 +198,8 @@ SYMBOLS = {
     "fdgs_render_contrib": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p]),
     "fdgs_render_features": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_int, c_int,
                                      c_void_p, c_float, c_void_p, c_void_p]),
+    "fdgs_render_features_bwd": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p,
+                                         c_float, c_void_p, c_int, c_void_p, c_int]),
 }
 CURVES = {"hilbert": 0, "morton": 1}      # FDGS_CURVE_*
 RGB8_MODES = {"trunc": 0, "round": 1}     # FDGS_RGB8_*

@@ -315,10 +315,10 @@ class Composite:
         (There is no Composite.select_rows: select per model with `Baked.select_rows`, then compose again.)"""
 
     def render_features(self, viewpoint_camera, pipe, bg_color, values, normalize=False, min_alpha=1e-4, scaling_modifier=1.0, cam_type=None,
-                        interp="linear", rgb8=None):
+                        interp="linear", rgb8=None, differentiable=False):
         return _render_features_state("Composite.render_features", self, lambda t: self.state_at(t, interp), self.active_sh_degree, self.device,
                                       *self._maps, viewpoint_camera, pipe, bg_color, values, normalize, min_alpha, scaling_modifier, cam_type,
-                                      rgb8)
+                                      rgb8, differentiable)
 
     render_features.__doc__ = _FEATURES_DOC + """
         The rows of `values` are rows of the whole scene (sum(N), model m's at `slices[m]`); with `model_indicator()` as the values the

@@ -14,6 +14,8 @@
 // blend weight over the pixels, the pixels and the tiles that show it --, one atomic record per (tile, entry); it writes nothing into the frame.
 // Feature pass (render_features_kernel): that walk with C per-row channels in place of the colour, sixteen per workgroup and all C in one launch,
 // each with the bits a forward blend of it would give; it writes nothing into the frame.
+// Feature pass backward (render_features_bwd_kernel, render_features_bwd.h): that walk once more for the gradient of the features to the values,
+// the sum over a tile's pixels as a contraction on the matrix cores, one atomic per (tile, entry, channel); it writes nothing into the frame.
 // Tile rows are dealt to the XCDs in groups (unit_of_block: workgroup b runs on XCD b % 8), so that neighbouring tiles -- which list
 // the same Gaussians -- share an XCD's 4 MiB L2 and every XCD owns rows from the whole height of the image.
 // Replaces renderCUDA forward/backward of the un-vendored rasterizer (Appendix B.3/B.4).
@@ -545,6 +547,8 @@ __global__ void __launch_bounds__(256) render_features_kernel(FeatArgs a) {
         if (a.alpha && blockIdx.y == 0) a.alpha[pix] = A;
     }
 }
+
+#include "render_features_bwd.h"      // the feature pass's adjoint with respect to its values: render_features_bwd_kernel
 
 // ---- wave64 all-reduce (sum): DPP inside rows, permlane swaps across rows; every lane ends with the total ----
 template <int CTRL>
@@ -1223,6 +1227,43 @@ extern "C" int fdgs_render_features(void* stream_, const fdgs_raster_params* p, 
         hipLaunchKernelGGL(render_features_kernel, dim3(unit_grid(a.gx, a.gy, 1, a.bh), (C + FEAT_CH - 1) / FEAT_CH), dim3(256), 0, stream, a);
     }
     FDGS_LAUNCH_CHECK("render_features", p->debug, stream);
+    return FDGS_OK;
+}
+
+extern "C" int fdgs_render_features_bwd(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
+                                        uint32_t R, int C, const float* dL_dfeatures, const float* alpha_opt, float min_alpha,
+                                        const int32_t* row_map_opt, int rows, float* dvalues, int dvalue_stride) {
+    FDGS_REQUIRE(p && geom && binning && img && dL_dfeatures && dvalues, "NULL pointer (params, geom, binning, img, dL_dfeatures and dvalues)");
+    FDGS_REQUIRE(p->P >= 0 && p->W >= 1 && p->H >= 1, "bad P/W/H");
+    FDGS_REQUIRE((p->W + TILE - 1) / TILE < 65536 && (p->H + TILE - 1) / TILE < 65536, "image too large");
+    FDGS_REQUIRE(C >= 1 && C <= 8 * 65535, "bad C (1 .. 8 * 65535 channels)");
+    FDGS_REQUIRE(dvalue_stride >= C, "bad dvalue_stride (at least C floats per row)");
+    FDGS_REQUIRE(rows >= 0, "bad rows (negative)");
+    const bool normalized = min_alpha >= 0.0f;                              // (negative or NaN: the forward wrote raw sums)
+    FDGS_REQUIRE(!normalized || alpha_opt, "NULL alpha_opt with min_alpha >= 0 (the alpha image the normalised forward wrote)");
+    FDGS_REQUIRE(aligned_to(dL_dfeatures, 4) && aligned_to(alpha_opt, 4) && aligned_to(row_map_opt, 4) && aligned_to(dvalues, 4),
+                 "arrays must be 4-byte aligned");
+    if (p->P == 0 || R == 0) return FDGS_OK;          // nothing was blended: nothing is accumulated, nothing is launched
+    hipStream_t stream = (hipStream_t)stream_;
+    // (of *p only P, W, H and debug are read and none of its pointers is looked at: a later frame may have overwritten what they named)
+    const GeomLayout gl = geom_layout(p->P);
+    const BinLayout bl = bin_layout(R);
+    const ImgLayout il = img_layout(p->W, p->H);
+    FeatBwdArgs a{};
+    a.W = p->W; a.H = p->H; a.gx = il.gx; a.gy = il.gy; a.bh = XCD_ROWS; a.per_xcd = il.per_xcd;
+    a.ranges = at<uint2>(img, il.ranges); a.pair_gid = at<uint32_t>(binning, bl.gid0);
+    a.recA = at<float4>(geom, gl.recA); a.recB = at<float4>(geom, gl.recB);
+    a.n_contrib = at<uint32_t>(img, il.n_contrib); a.tile_todo = at<uint32_t>(img, il.todo);
+    a.R = R; a.P = p->P;
+    a.C = C; a.grad = dL_dfeatures; a.alpha = normalized ? alpha_opt : nullptr; a.min_alpha = normalized ? min_alpha : -1.0f;
+    a.row_map = row_map_opt; a.rows = rows; a.dvalues = dvalues; a.dvalue_stride = dvalue_stride;
+    // the forward's own heaviest-first order, where fdgs_render_fwd wrote one (make_tile_order's condition); never rebuilt here
+    a.order = tiles_ordered(il) ? at<uint32_t>(img, il.order_f) : nullptr;
+    {
+        FDGS_TIMED("render_features_bwd", stream);
+        hipLaunchKernelGGL(render_features_bwd_kernel, dim3(unit_grid(a.gx, a.gy, 1, a.bh), (C + FEAT_CH - 1) / FEAT_CH), dim3(256), 0, stream, a);
+    }
+    FDGS_LAUNCH_CHECK("render_features_bwd", p->debug, stream);
     return FDGS_OK;
 }
 

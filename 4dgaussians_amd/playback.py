@@ -440,11 +440,47 @@ def _checked_values(who, values, N, device):
     return v, C, stride
 
 
+class _FeaturesFrame:
+    """What the backward of a differentiable feature pass needs of its frame: the RasterState (geom, binning, img, capacity, params), the
+    owner's row map (None: the model's order), the alpha image, whether and from which alpha on the forward normalised, and N, C.  Kept
+    by the autograd graph of "features": a pending graph pins ONE frame's buffers, nothing else of the owner."""
+    __slots__ = ("rstate", "row_map", "alpha", "normalize", "min_alpha", "N", "C", "features")
+
+
+class _FeaturesOfValues(torch.autograd.Function):
+    """"features" as a function of `values`: the forward hands out the image fdgs_render_features wrote (the plain pass's bits), the backward
+    is ONE fdgs_render_features_bwd over the same frame's lists into a zeroed [N,C].  Nothing is consumed: a second backward of a retained
+    graph runs the same call again.  Not differentiable twice; no gradient reaches the geometry."""
+
+    @staticmethod
+    def forward(ctx, values, frame):
+        ctx.frame, ctx.values_shape = frame, tuple(values.shape)
+        ctx.set_materialize_grads(False)
+        features, frame.features = frame.features, None
+        return features
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        if grad is None:
+            return None, None
+        f = ctx.frame
+        rstate = f.rstate
+        g = grad.to(torch.float32).contiguous()
+        dvalues = torch.zeros(f.N, f.C, dtype=torch.float32, device=g.device)
+        _lib.check(_lib.lib().fdgs_render_features_bwd(_lib.stream_ptr(), rstate.params, _lib.ptr(rstate.geom), _lib.ptr(rstate.binning),
+                                                       _lib.ptr(rstate.img), rstate.capacity, f.C, _lib.ptr(g),
+                                                       _lib.ptr(f.alpha) if f.normalize else None, f.min_alpha if f.normalize else -1.0,
+                                                       _lib.ptr(f.row_map), f.N, _lib.ptr(dvalues), f.C))
+        return dvalues.view(ctx.values_shape), None
+
+
 def _render_features_state(who, owner, frame_at, sh_degree, device, to_stored, to_model, viewpoint_camera, pipe, bg_color, values, normalize,
-                           min_alpha, scaling_modifier, cam_type, rgb8):
+                           min_alpha, scaling_modifier, cam_type, rgb8, differentiable=False):
     """The body of Baked.render_features, SparseBaked.render_features and Composite.render_features: the frame of _render_state, then ONE
     fdgs_render_features over the RasterState it left behind (include/fdgs.h: one more walk over the frame's own sorted lists, which writes
-    nothing into them), reading `values` in place through the owner's stored -> model row map."""
+    nothing into them), reading `values` in place through the owner's stored -> model row map.  `differentiable` with grad mode on and
+    values that require grad: the same calls, and "features" leaves through _FeaturesOfValues."""
     if pipe.compute_cov3D_python or pipe.convert_SHs_python:
         raise NotImplementedError(f"{who}: pipe.compute_cov3D_python / pipe.convert_SHs_python need the live model; use fdgs.render")
     v, C, stride = _checked_values(who, values, owner.N, device)
@@ -467,7 +503,12 @@ def _render_features_state(who, owner, frame_at, sh_degree, device, to_stored, t
                                                    rstate.capacity, C, v.data_ptr(), stride, owner.N, _lib.ptr(owner._pick_row_map),
                                                    min_alpha if normalize else -1.0, _lib.ptr(features), _lib.ptr(alpha)))
         out["features"], out["alpha"] = features, alpha
-        return out
+    if differentiable and torch.is_grad_enabled() and values.requires_grad:
+        f = _FeaturesFrame()
+        f.rstate, f.row_map, f.alpha, f.normalize, f.min_alpha, f.N, f.C = rstate, owner._pick_row_map, alpha, bool(normalize), min_alpha, owner.N, C
+        f.features = features
+        out["features"] = _FeaturesOfValues.apply(values, f)
+    return out
 
 
 _FEATURES_DOC = """Everything `render(viewpoint_camera, pipe, bg_color, scaling_modifier, cam_type=cam_type, interp=interp, rgb8=rgb8)` returns,
@@ -481,7 +522,15 @@ _FEATURES_DOC = """Everything `render(viewpoint_camera, pipe, bg_color, scaling_
           "alpha"    float32 [1,H,W]  the accumulated alpha, the sum of w.
         `values`: a float32 [N] or [N,C] tensor on the device in the row order of "radii" (a per-model indicator, `motion_extent`, a
         `Contribution` column, labels, normals, embeddings); read in place -- it need not be contiguous as long as its last dimension
-        has stride 1, e.g. a column slice of a wider array.  Anything else: ValueError."""
+        has stride 1, e.g. a column slice of a wider array.  Anything else: ValueError.
+        `differentiable=True`, with grad mode on and `values.requires_grad`: "features" (the same bits, from the same calls) carries the
+        gradient to `values` -- d features[c, pixel] / d values[row, c] = w, or w / "alpha" where normalised --, computed by ONE
+        fdgs_render_features_bwd over this frame's own lists per backward, in the shape of `values`; what a frozen model's per-row
+        embeddings, labels or identities are fitted to 2-D masks and feature maps with.  Nothing else is differentiable: "alpha", every
+        key of `render`, and the geometry behind the weights (the path through "alpha" of a normalised pass included).  The graph of
+        "features" holds this frame's rasterizer buffers until it is freed -- a pending graph pins one frame's buffers --, and a
+        backward may run after later frames were rendered, any number of times (retain_graph).  The gradient image must be finite.
+        Otherwise (the default, no_grad, values without requires_grad): exactly the plain pass."""
 
 
 class _AtTime:
@@ -600,10 +649,10 @@ class Baked:
     render_contrib.__doc__ = _CONTRIB_DOC
 
     def render_features(self, viewpoint_camera, pipe, bg_color, values, normalize=False, min_alpha=1e-4, scaling_modifier=1.0, cam_type=None,
-                        interp="linear", rgb8=None):
+                        interp="linear", rgb8=None, differentiable=False):
         return _render_features_state("Baked.render_features", self, lambda t: self.state_at(t, interp)[0], self.active_sh_degree, self.device,
                                       *self._maps, viewpoint_camera, pipe, bg_color, values, normalize, min_alpha, scaling_modifier, cam_type,
-                                      rgb8)
+                                      rgb8, differentiable)
 
     render_features.__doc__ = _FEATURES_DOC
 
@@ -846,10 +895,10 @@ class SparseBaked:
         (There is no SparseBaked.select_rows: select on the dense bake, or prune the model, and bake sparse again.)"""
 
     def render_features(self, viewpoint_camera, pipe, bg_color, values, normalize=False, min_alpha=1e-4, scaling_modifier=1.0, cam_type=None,
-                        interp="linear", rgb8=None):
+                        interp="linear", rgb8=None, differentiable=False):
         return _render_features_state("SparseBaked.render_features", self, lambda t: self.state_at(t, interp)[0], self.active_sh_degree,
                                       self.device, *self._maps, viewpoint_camera, pipe, bg_color, values, normalize, min_alpha,
-                                      scaling_modifier, cam_type, rgb8)
+                                      scaling_modifier, cam_type, rgb8, differentiable)
 
     render_features.__doc__ = _FEATURES_DOC
 

@@ -793,6 +793,49 @@ int fdgs_render_features(void* stream, const fdgs_raster_params* p, const void* 
                          uint32_t num_rendered, int C, const float* values, int value_stride, int rows,
                          const int32_t* row_map_opt, float min_alpha, float* features /* [C,H,W] */, float* alpha_opt /* [H,W] */);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Feature pass backward (an addition to ABI 6; no existing signature changed): the adjoint of fdgs_render_features with respect to its
+ * values -- what a method that freezes a trained model and optimises one embedding, label or identity per Gaussian against 2-D masks or
+ * feature maps needs for a training step -- by ONE more walk over the same finished frame's sorted lists (csrc/render_features_bwd.h:
+ * render_features_bwd_kernel, fdgs.playback.Baked.render_features(differentiable=True)):
+ *
+ *     dvalues[row * dvalue_stride + c] += sum over the pixels of w(row, pixel) * dL_dfeatures[c, pixel]
+ *
+ * with the w of the forward: the same walk, decisions and expressions (the pick pass's), so w has the bits the forward multiplied the
+ * values with.  The sum over a tile's 256 pixels is a contraction on the matrix cores (v_mfma_f32_16x16x4_f32: float32 products and
+ * sums, no reduced-precision operand); the order of the additions inside a tile and across tiles is not fixed.  For a normalised forward
+ * (min_alpha >= 0) a pixel's gradient is scaled on load, dL_dfeatures[c, pixel] / A (IEEE division) where A = alpha_opt[pixel] >
+ * min_alpha and 0 elsewhere.  This is the gradient with respect to `values` ONLY: the path through A, like every other path into the
+ * geometry, is not followed (a bake has no live geometry to receive it).
+ * A NON-FINITE dL_dfeatures IS OUT OF CONTRACT: the contraction multiplies the zero weights of a tile's skipped entries with every
+ * gradient of the wave's 64 pixels, so one inf or NaN reaches (0 * inf) rows that do not contribute to its pixel.
+ *
+ * Valid wherever fdgs_render_features is valid, with the same geom, binning, img and num_rendered -- for as long as those buffers still
+ * hold the frame.  OF *p ONLY P, W, H AND debug ARE READ, AND NONE OF ITS POINTERS IS DEREFERENCED OR COPIED: by the time a backward
+ * runs, a later fdgs_state_at may have overwritten the states the frame was projected from; what the walk needs lives in geom, binning
+ * and img.
+ * -------------------------------------------------------------------------------------------------------- */
+/* dL_dfeatures: device float[C*H*W], plane c at dL_dfeatures + c * H * W.  alpha_opt: device float[H*W], the alpha image that forward
+ * wrote; required when min_alpha >= 0, not read otherwise (min_alpha < 0 or NaN: the forward wrote raw sums).
+ * dvalues: device float, row r at dvalues + r * dvalue_stride, dvalue_stride >= C floats; ACCUMULATED into, never cleared by the call
+ * (like fdgs_contrib_row): zero it before the first pass, accumulate any number of frames.  Gaussian g goes to row row_map_opt ?
+ * row_map_opt[g] : g (row_map_opt: device int32[P] or NULL); a row outside [0, rows) -- a -1 of the map included -- is dropped.  Only
+ * 4-byte alignment is required of it; where rows are 64-byte aligned one atomic instruction covers whole rows.  Floats of a row behind
+ * its C channels are not touched.
+ * FDGS_E_INVALID with a message, before anything is launched, for: a NULL params, geom, binning, img, dL_dfeatures or dvalues; W or H
+ * < 1; C < 1 or C > 8 * 65535; dvalue_stride < C; rows < 0; min_alpha >= 0 with a NULL alpha_opt; dL_dfeatures, alpha_opt, row_map_opt
+ * or dvalues not 4-byte aligned.  P == 0 or num_rendered == 0 succeeds without touching dvalues (and without a launch).  Otherwise ONE
+ * launch on `stream` for any C (chunks of sixteen channels, one workgroup per tile and chunk), nothing synchronises (params->debug
+ * aside); its row in fdgs_timing_report is "render_features_bwd".  At most one float atomic per (tile, list entry, channel); a zero sum
+ * issues none, so a row no pixel shows keeps its bits.
+ * It WRITES NOTHING into the frame -- geom, binning and img keep their bits; the tiles are taken in the order the forward left in img
+ * field 4, which is read, not rebuilt --, so it may run any number of times, before or after a pick, contribution or motion pass.  A
+ * stale img cannot make it read past a list: every walk is clamped to the tile's range, the tile's walk length and num_rendered. */
+int fdgs_render_features_bwd(void* stream, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
+                             uint32_t num_rendered, int C, const float* dL_dfeatures /* [C,H,W] */,
+                             const float* alpha_opt /* [H,W], required when min_alpha >= 0 */, float min_alpha,
+                             const int32_t* row_map_opt, int rows, float* dvalues, int dvalue_stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -332,7 +332,48 @@ def check16(W, F, k, rng):
     return True
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The feature pass's backward (csrc/render_features_bwd.h): per wave dV[entry][channel] = sum over its 64 pixels of w[entry][pixel] *
+# G[channel][pixel] as 16 v_mfma_f32_16x16x4_f32.  Both operands start as 16 registers of [k][lane = pixel] and go through the wave's LDS
+# park (rows PARK floats apart): register s of lane l becomes element [l & 15][s + 16 (l >> 4)].
+PARK = 65
+
+
+def park_transpose(M):
+    """M [16][64] (register k of lane p) -> [16][64] (register s of lane l), through the park's addresses."""
+    park = np.full(16 * PARK, np.nan)
+    for k in range(16):
+        park[k * PARK + LANES] = M[k]
+    return np.stack([park[N16 * PARK + 16 * Q16 + s] for s in range(16)])
+
+
+def check_features_bwd(rng):
+    w, G = rng.standard_normal((16, 64)), rng.standard_normal((16, 64))
+    wt, gt = park_transpose(w), park_transpose(G)
+    acc = np.zeros((64, 4))
+    for s in range(16):
+        acc = mfma16(wt[s], gt[s], acc)
+    dV = np.zeros((16, 16))
+    for r in range(4):
+        dV[4 * Q16 + r, N16] = acc[:, r]            # register r of lane l: entry 4 (l >> 4) + r, channel l & 15
+    assert np.allclose(dV, w @ G.T), "features backward"
+    # the wave's result slot: register r of lane l at word 64 r + l; flush thread t reads word t as entry 4 ((t >> 4) & 3) + (t >> 6), channel t & 15
+    slot = np.concatenate([acc[:, r] for r in range(4)])
+    t = np.arange(256)
+    flushed = np.zeros((16, 16))
+    flushed[4 * ((t >> 4) & 3) + (t >> 6), t & 15] = slot[t]
+    assert np.array_equal(flushed, dV), "features backward: slot"
+    # the park's banks (ds_write_b32 / ds_read_b32: 32 banks, lanes of a 32-lane half conflict): every write and read is conflict-free
+    for half in (LANES[:32], LANES[32:]):
+        for k in range(16):
+            assert len(set((k * PARK + half) % 32)) == 32
+            assert len(set(((half & 15) * PARK + 16 * (half >> 4) + k) % 32)) == 32
+    return True
+
+
 if __name__ == "__main__":
+    check_features_bwd(np.random.default_rng(2))
+    print("features backward: layouts consistent, park conflict-free")
     for W, F, k in [(128, 32, 3), (128, 32, 48), (64, 64, 4), (128, 48, 1), (64, 32, 48)]:
         check16(W, F, k, np.random.default_rng(1))
         print(f"16-Gaussian forms W={W} F={F} k={k}: layouts consistent")
