@@ -162,8 +162,10 @@ __device__ __forceinline__ void wgrad_wave(const WgradJob& J, int W, const_u32p 
 
 template <int WT, bool ROWS>
 __global__ void __launch_bounds__(256, 1) deform_wgrad_kernel(WgradArgs a) {
-    constexpr int W = WT * 32;
-    __shared__ __attribute__((aligned(16))) float lds[W * W + W];
+    // the accumulator rows are ldl floats wide: W for the head products, 32 * ceil(C*L / 32) <= 128 for the trunk product -- which is WIDER than
+    // W at net_width 64 with C*L = 96 / 128 (W * W floats were too few there: rows past the array were dropped and the bias row overlapped)
+    constexpr int W = WT * 32, LDM = W > 128 ? W : 128;
+    __shared__ __attribute__((aligned(16))) float lds[W * LDM + W];
     // job of this workgroup
     int j = 0;
 #pragma unroll
@@ -182,7 +184,7 @@ __global__ void __launch_bounds__(256, 1) deform_wgrad_kernel(WgradArgs a) {
     if (wb > t1) wb = t1;
     if (we > t1) we = t1;
     float* ldsW = lds;
-    float* ldsB = lds + W * W;
+    float* ldsB = lds + W * LDM;
     const int CTn = (J.ncols + 31) / 32;
     // (every wave joins, also one whose slice is empty: the reduction inside is a workgroup-wide protocol)
     if (J.ncols == W) wgrad_wave<WT, WT, true, 8, ROWS>(J, W, live_list, wb, we, ldsW, ldsB, g, h, wave);

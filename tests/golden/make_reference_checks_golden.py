@@ -48,9 +48,10 @@ for cfg in RC.DEFORM_CFGS:
     sd = RefNet(syn.deform_args(cfg)).state_dict()
     out[f"layout.{cfg}"] = np.array([RC.layout_entry(k, v) for k, v in sd.items()], dtype=str)
 
-# ---- deform_network forward + backward (tests/test_oracle_deform.py): this repository's seeded network loaded into the reference's
-for cfg in RC.DEFORM_CFGS:
-    args = syn.deform_args(cfg)
+# ---- deform_network forward + backward (tests/test_oracle_deform.py): this repository's seeded network loaded into the reference's,
+# at the named configs and at the shapes of RC.DEFORM_SHAPE_CASES
+for cfg in RC.DEFORM_CFGS + tuple(RC.DEFORM_SHAPE_CASES):
+    args = RC.deform_args(cfg)
     net = RefNet(args)
     net.load_state_dict(RC.seeded_deform_state(cfg), strict=True)
     xyz, sc, rot, op, shs, t = [x.clone().requires_grad_(i < 5) for i, x in enumerate(RC.deform_inputs())]

@@ -15,6 +15,16 @@ PATH = os.path.join(GOLD, "reference_checks.npz")
 GM_METHODS = ("add_densification_stats", "prune_points", "prune", "reset_opacity", "densify", "save_ply", "load_ply", "save_deformation",
               "load_model", "compute_regulation")
 DEFORM_CFGS = ("dnerf_bouncingballs", "hypernerf_default", "dynerf_default")
+# deform_network shapes that no named config has: name -> (config it starts from, overrides of synthetic.deform_args, kplanes_config entries).
+# "refdefaults": the reference's own argument defaults (arguments/__init__.py: net_width 64, defor_depth 1, output_coordinate_dim 32,
+# multires [1, 2, 4, 8], position / scale / rotation heads); the other: net_width 128 at C * L = 96 with a head set no config has.  The base
+# resolution is small so that the recorded plane gradients stay below the largest file of tests/golden.
+DEFORM_SHAPE_CASES = {
+    "refdefaults": ("dnerf_bouncingballs", dict(net_width=64, defor_depth=1, multires=[1, 2, 4, 8]),
+                    dict(output_coordinate_dim=32, resolution=[16, 16, 16, 10])),
+    "w128_f96_heads_x_o_shs": ("dynerf_default", dict(net_width=128, defor_depth=0, multires=[1, 2, 4], no_ds=True, no_dr=True),
+                               dict(output_coordinate_dim=32, resolution=[16, 16, 16, 10])),
+}
 DENSIFY_CASES = ((300, 3, 20), (64, 4, None), (1, 5, 20))
 LOSS_SHAPES = ((1, 3, 11, 11), (2, 3, 40, 64), (1, 1, 5, 70))
 SMOOTH_SHAPES = ((1, 16, 75, 64), (1, 32, 3, 5), (2, 4, 10, 7))
@@ -52,11 +62,22 @@ def deform_inputs():
     return g["xyz"], g["scaling"], g["rotation"], g["opacity"], shs, t
 
 
+def deform_args(cfg):
+    """The deform_network arguments of a named config or of one of DEFORM_SHAPE_CASES."""
+    syn = importlib.import_module("4dgaussians_amd.synthetic")
+    if cfg not in DEFORM_SHAPE_CASES:
+        return syn.deform_args(cfg)
+    base, overrides, kplanes = DEFORM_SHAPE_CASES[cfg]
+    args = syn.deform_args(base, **overrides)
+    args.kplanes_config.update(kplanes)
+    return args
+
+
 def seeded_deform_state(cfg):
     """State dict of this repository's deform_network for `cfg` (seeded, HexPlane grids perturbed, aabb of deform_inputs())."""
     fdgs = importlib.import_module("4dgaussians_amd")
     torch.manual_seed(6666)
-    net = fdgs.deform_network(fdgs.synthetic.deform_args(cfg))
+    net = fdgs.deform_network(deform_args(cfg))
     gen = torch.Generator().manual_seed(6667)
     with torch.no_grad():
         for name, p in net.named_parameters():

@@ -21,17 +21,20 @@ def _fdgs():
     return importlib.import_module("4dgaussians_amd")
 
 
-def _net_and_inputs(cfg, n, seed, dev, overrides=None, safe=True, fixed_time=None):
+def _net_and_inputs(cfg, n, seed, dev, overrides=None, safe=True, fixed_time=None, candidates=None, kplanes=None):
+    """`overrides`: fields of synthetic.deform_args; `kplanes`: entries of its kplanes_config (output_coordinate_dim, resolution);
+    `candidates`: rows drawn before the safe ones are picked (default 2n + 64; the share of safe rows falls with net_width and levels)."""
     fd = _fdgs()
     torch.manual_seed(seed)
     args = synthetic.deform_args(cfg, **(overrides or {}))
+    args.kplanes_config.update(kplanes or {})
     net = fd.deform_network(args)
     gen = torch.Generator().manual_seed(seed)
     with torch.no_grad():
         for name, p in net.named_parameters():
             if "grids" in name:
                 p.add_(0.1 * torch.randn(p.shape, generator=gen))
-    m = 2 * n + 64 if safe else n
+    m = (2 * n + 64 if candidates is None else candidates) if safe else n
     g = synthetic.make_gaussians(m, seed=seed)
     xyz = g["xyz"] * 1.05  # a few points outside the aabb: border clamp + zero coordinate gradient
     net.deformation_net.set_aabb([1.3, 1.25, 1.2], [-1.3, -1.2, -1.25])
@@ -102,33 +105,53 @@ def test_deform_parity_recompute_path(cfg, n, monkeypatch):
     _parity(cfg, n, True)
 
 
-def _parity(cfg, n, activate, scalar_time=None):
+def _parity_cpu_side(cfg, n, activate, scalar_time, overrides, kplanes, candidates):
+    """The CPU half of _parity: network, safe inputs, the oracle's outputs and its gradients of sum(out * w)."""
     dev = torch.device("cuda:0")
-    fd = _fdgs()
-    args, net, ins = _net_and_inputs(cfg, n, 3, dev, fixed_time=scalar_time)
+    args, net, ins = _net_and_inputs(cfg, n, 3, dev, overrides=overrides, fixed_time=scalar_time, candidates=candidates, kplanes=kplanes)
     # oracle on CPU with the same state dict
     sd = {k: v.detach().clone().contiguous().requires_grad_(v.dtype.is_floating_point and "poc" not in k and "aabb" not in k)
           for k, v in net.state_dict().items()}
     cpu_in = [x.clone().requires_grad_(i < 5) for i, x in enumerate(ins)]
     ref = DO.deform_forward(sd, args, *cpu_in, activate=activate)
-    net = net.to(dev)
-    gpu_in = [x.to(dev).requires_grad_(i < 5) for i, x in enumerate(ins)]
-    out = fd.deformation.deform(net, *gpu_in[:4], shs=gpu_in[4], time=gpu_in[5] if scalar_time is None else float(scalar_time),
-                                activate=activate)
-    torch.cuda.synchronize()
-    names = ("xyz", "scales", "rot", "opacity", "shs")
-    for k, a, b in zip(names, out, ref):
-        e = rel_l2(a.detach().cpu().numpy(), b.detach().numpy().reshape(a.shape))
-        assert e < 2e-5, (k, e)
     gen = torch.Generator().manual_seed(11)
     ws = [torch.randn(b.shape, generator=gen) for b in ref]
     loss_ref = sum((a * w).sum() for a, w in zip(ref, ws))
     params_cpu = [sd[k] for k in sd if sd[k].requires_grad]
     pnames = [k for k in sd if sd[k].requires_grad]
     g_ref = torch.autograd.grad(loss_ref, cpu_in[:5] + params_cpu, allow_unused=True)
+    return dict(args=args, net=net.to(dev), ins=ins, ref=[b.detach() for b in ref], ws=ws, pnames=pnames, g_ref=g_ref)
+
+
+def _parity(cfg, n, activate, scalar_time=None, overrides=None, kplanes=None, candidates=None, ordered=None, shared=None, details=None):
+    """HIP forward and backward against the CPU oracle: outputs to rel-L2 < 2e-5, every gradient of sum(out * w) on safe rows to < 1e-4.
+    `overrides`, `kplanes`, `candidates`: see _net_and_inputs; `ordered`: handed to deform().  `shared`: a dict that keeps the CPU half (network,
+    inputs, oracle results: read-only) for further calls with the same arguments before it; `details`: a dict that receives the
+    forward's per-output rel-L2 ("fwd"), the network ("net"), the inputs ("ins") and the HIP outputs ("out") and gradients ("grads",
+    by name, on the CPU).  Returns the per-tensor rel-L2 of the gradients."""
+    dev = torch.device("cuda:0")
+    fd = _fdgs()
+    cpu = shared.get("cpu") if shared is not None else None
+    if cpu is None:
+        cpu = _parity_cpu_side(cfg, n, activate, scalar_time, overrides, kplanes, candidates)
+        if shared is not None:
+            shared["cpu"] = cpu
+    net, ins, ref, ws, pnames, g_ref = cpu["net"], cpu["ins"], cpu["ref"], cpu["ws"], cpu["pnames"], cpu["g_ref"]
+    gpu_in = [x.to(dev).requires_grad_(i < 5) for i, x in enumerate(ins)]
+    out = fd.deformation.deform(net, *gpu_in[:4], shs=gpu_in[4], time=gpu_in[5] if scalar_time is None else float(scalar_time),
+                                activate=activate, ordered=ordered)
+    torch.cuda.synchronize()
+    names = ("xyz", "scales", "rot", "opacity", "shs")
+    fwd = {k: rel_l2(a.detach().cpu().numpy(), b.numpy().reshape(a.shape)) for k, a, b in zip(names, out, ref)}
+    if details is not None:
+        details.update(fwd=fwd, net=net, ins=ins, out=[a.detach() for a in out])
+    for k, e in fwd.items():
+        assert e < 2e-5, (k, e)
     loss = sum((a * w.to(dev).reshape(a.shape)).sum() for a, w in zip(out, ws))
     params_gpu = [dict(net.named_parameters())[k] for k in pnames]
     g_gpu = torch.autograd.grad(loss, gpu_in[:5] + params_gpu, allow_unused=True)
+    if details is not None:
+        details["grads"] = {k: (None if a is None else a.cpu()) for k, a in zip(list(names) + pnames, g_gpu)}
     report = {}
     for k, a, b in zip(list(names) + pnames, g_gpu, g_ref):
         if b is None:
@@ -146,6 +169,7 @@ def _parity(cfg, n, activate, scalar_time=None):
             print(f"   {k}: rows with largest error {bad.tolist()} -> {np.round(rowerr[bad], 4).tolist()}")
     for k, v in report.items():
         assert v < 1e-4, (k, v)
+    return report
 
 
 def _grads_pair(cfg, n, seed, upstream_mask=None):
@@ -335,13 +359,28 @@ def test_module_api_matches_reference_signature_and_scalar_time():
     assert torch.equal(a[3], gi[3]) and torch.equal(a[4], gi[4])
 
 
-def _render_end_to_end_vs_oracle(cfg, stage, active_sh_degree=3, scaling_modifier=1.0, bg=(0.0, 0.0, 0.0)):
+def _render_end_to_end_vs_oracle(cfg, stage, active_sh_degree=3, scaling_modifier=1.0, bg=(0.0, 0.0, 0.0), overrides=None, kplanes=None,
+                                 n=4000, size=(200, 152)):
     """render() (deform -> activations -> rasterize) against oracle deform -> oracle rasterizer, image and every gradient, at the model's
-    active SH degree, a scale modifier and a background colour."""
+    active SH degree, a scale modifier and a background colour.  `overrides` / `kplanes` (fields of synthetic.deform_args / entries of its
+    kplanes_config): a deformation network of another shape, seeded, perturbed and bounded the way SynthModel does its own."""
     dev = torch.device("cuda:0")
     fd = _fdgs()
-    n, W, H = 4000, 200, 152
-    pc = synthetic.SynthModel(n, cfg, seed=21)
+    W, H = size
+    deformation = None
+    if overrides or kplanes:
+        torch.manual_seed(21)
+        args = synthetic.deform_args(cfg, **(overrides or {}))
+        args.kplanes_config.update(kplanes or {})
+        deformation = fd.deform_network(args)
+        gen = torch.Generator().manual_seed(22)
+        with torch.no_grad():
+            for name, p in deformation.named_parameters():
+                if "grids" in name:
+                    p.add_(0.1 * torch.randn(p.shape, generator=gen))
+        xyz = synthetic.make_gaussians(n, seed=21)["xyz"]
+        deformation.deformation_net.set_aabb(xyz.max(0).values.tolist(), xyz.min(0).values.tolist())
+    pc = synthetic.SynthModel(n, cfg, seed=21, deformation=deformation)
     pc.active_sh_degree = active_sh_degree
     cam = synthetic.make_camera(W, H, theta_deg=40.0, time=0.6)
     with torch.no_grad():

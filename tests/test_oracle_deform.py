@@ -20,12 +20,14 @@ def _inputs(n, seed=1):
     return g["xyz"], g["scaling"], g["rotation"], g["opacity"], shs
 
 
-@pytest.mark.parametrize("cfg", ["dnerf_bouncingballs", "hypernerf_default", "dynerf_default"])
+@pytest.mark.parametrize("cfg", ["dnerf_bouncingballs", "hypernerf_default", "dynerf_default", "refdefaults", "w128_f96_heads_x_o_shs"])
 def test_matches_reference_modules_fwd_bwd(cfg):
     """The reference's deform_network, loaded with a seeded network of this repository (grids perturbed), evaluated forward and
-    backward on seeded Gaussians: its outputs and every gradient are recorded in tests/golden/reference_deform_<cfg>.npz."""
+    backward on seeded Gaussians: its outputs and every gradient are recorded in tests/golden/reference_deform_<cfg>.npz.
+    Beside the three named configs: the reference's own argument defaults (net_width 64, C 32, four levels, defor_depth 1: C * L = 128)
+    and net_width 128 at C * L = 96 with the position, opacity and SH heads (reference_checks.DEFORM_SHAPE_CASES)."""
     Z = RC.load(RC.deform_path(cfg))
-    args = synthetic.deform_args(cfg)
+    args = RC.deform_args(cfg)
     net = importlib.import_module("4dgaussians_amd").deform_network(args)
     net.load_state_dict(RC.seeded_deform_state(cfg), strict=True)
     xyz, sc, rot, op, shs, t = [x.clone().requires_grad_(i < 5) for i, x in enumerate(RC.deform_inputs())]
