@@ -139,6 +139,9 @@ SYMBOLS = {
     "fdgs_mark_visible": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdgs_preprocess_host": (c_int, [POINTER(RasterParams)] + [c_void_p] * 9),
     "fdgs_preprocess_bwd_host": (c_int, [POINTER(RasterParams)] + [c_void_p] * 13),
+    "fdgs_camera_grad_scratch_bytes": (c_int, [c_int, POINTER(c_size_t)]),
+    "fdgs_camera_grad": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fdgs_camera_grad_host": (c_int, [POINTER(RasterParams)] + [c_void_p] * 8),
     "fdgs_geom_field": (c_int, [c_void_p, c_int, c_int, POINTER(c_void_p)]),
     "fdgs_binning_field": (c_int, [c_void_p, c_uint32, c_int, c_int, c_int, POINTER(c_void_p)]),
     "fdgs_img_field": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_void_p)]),

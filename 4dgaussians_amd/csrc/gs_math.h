@@ -309,9 +309,11 @@ FDGS_HD void mean2d_grad_to_ndc(float gx_pix, float gy_pix, int W, int H, float*
     g_ndc[0] = gx_pix * 0.5f * (float)W; g_ndc[1] = gy_pix * 0.5f * (float)H;
 }
 
-// conic / depth / mean2D gradients -> dmean (+=), dcov6 (written)
-FDGS_HD void project_bwd(const CamConst& c, const float* p, const float* c6, const float* dconic /*xx, xy(half), yy*/,
-                         float ddepth, float g_ndc_x, float g_ndc_y, float* dmean, float* dcov6) {
+// The part of project_bwd the camera's gradient shares with it (camera_terms below): conic / depth gradients -> dcov6 (written),
+// dpv = dL/d(view-space centre) = (dtx, dty, dtz) with the clamp flags and the depth term applied, dM = dL/d(J*Rv) (2x3) and
+// J = (J00, J02, J11, J12) of the clamped centre.
+FDGS_HD void project_bwd_view(const CamConst& c, const float* p, const float* c6, const float* dconic /*xx, xy(half), yy*/,
+                              float ddepth, float* dcov6, float* dpv, float* dM, float* J) {
     float pv[3];
     view_xform(c.view, p, pv);
     float Mx[6], tc[3], abc[3], MS[6];
@@ -344,7 +346,6 @@ FDGS_HD void project_bwd(const CamConst& c, const float* p, const float* c6, con
     dcov6[4] = 2.0f * (Mx[1] * GM[2] + Mx[4] * GM[5]);
     dcov6[5] = Mx[2] * GM[2] + Mx[5] * GM[5];
     const float S[9] = {c6[0], c6[1], c6[2], c6[1], c6[3], c6[4], c6[2], c6[4], c6[5]};
-    float dM[6];
 #pragma unroll
     for (int r = 0; r < 2; r++)
 #pragma unroll
@@ -360,6 +361,18 @@ FDGS_HD void project_bwd(const CamConst& c, const float* p, const float* c6, con
     float dtz = -c.focal_x * tz2 * dJ00 - c.focal_y * tz2 * dJ11 + (2.0f * c.focal_x * tc[0]) * tz3 * dJ02 +
                 (2.0f * c.focal_y * tc[1]) * tz3 * dJ12;
     dtz += ddepth;  // depth_i = p_view.z
+    dpv[0] = dtx; dpv[1] = dty; dpv[2] = dtz;
+    J[0] = c.focal_x / tc[2]; J[1] = -(c.focal_x * tc[0]) / (tc[2] * tc[2]);       // as ewa_M forms them
+    J[2] = c.focal_y / tc[2]; J[3] = -(c.focal_y * tc[1]) / (tc[2] * tc[2]);
+}
+
+// conic / depth / mean2D gradients -> dmean (+=), dcov6 (written)
+FDGS_HD void project_bwd(const CamConst& c, const float* p, const float* c6, const float* dconic /*xx, xy(half), yy*/,
+                         float ddepth, float g_ndc_x, float g_ndc_y, float* dmean, float* dcov6) {
+    float dpv[3], dM[6], J[4];
+    project_bwd_view(c, p, c6, dconic, ddepth, dcov6, dpv, dM, J);
+    const float dtx = dpv[0], dty = dpv[1], dtz = dpv[2];
+    const float* v = c.view;
     dmean[0] += v[0] * dtx + v[1] * dty + v[2] * dtz;
     dmean[1] += v[4] * dtx + v[5] * dty + v[6] * dtz;
     dmean[2] += v[8] * dtx + v[9] * dty + v[10] * dtz;
@@ -372,6 +385,46 @@ FDGS_HD void project_bwd(const CamConst& c, const float* p, const float* c6, con
     dmean[0] += (pr[0] * mw - pr[3] * mul1) * g_ndc_x + (pr[1] * mw - pr[3] * mul2) * g_ndc_y;
     dmean[1] += (pr[4] * mw - pr[7] * mul1) * g_ndc_x + (pr[5] * mw - pr[7] * mul2) * g_ndc_y;
     dmean[2] += (pr[8] * mw - pr[11] * mul1) * g_ndc_x + (pr[9] * mw - pr[11] * mul2) * g_ndc_y;
+}
+
+// One visible Gaussian's share of the camera's gradient, from the same sums project_bwd and sh_bwd take (row-vector convention, row-major
+// matrices v[4*r + c]).  t[27], written:
+//   t[3*r + c]       = dL/dviewmatrix[4*r + c], c < 3 (column 3 is exactly 0): ph_r * dpv_c, ph = (x, y, z, 1), plus for r < 3 the covariance
+//                      path sum_k J[k][c] * dM[k][r]  (M = J*Rv, Rv[i][j] = v[4*j + i])
+//   t[12 + 3*r + k]  = dL/dprojmatrix[4*r + c], c = (0, 1, 3)[k] (column 2 is exactly 0): ph_r * dhom_c, dhom the derivative of the NDC position
+//                      through mw = 1 / (w + FDGS_W_EPS) (the terms behind mul1 / mul2 of project_bwd)
+//   t[24 + k]        = dL/dcampos[k]: minus what sh_bwd adds to dmean (colour clamp mask applied there); 0 without SH (sh == NULL)
+FDGS_HD void camera_terms(const CamConst& c, const float* p, const float* c6, const float* dconic /*xx, xy(half), yy*/, float ddepth,
+                          float g_ndc_x, float g_ndc_y, const float* sh, uint32_t clamped, const float* dL_drgb, float* t) {
+    float dcov6[6], dpv[3], dM[6], J[4];
+    project_bwd_view(c, p, c6, dconic, ddepth, dcov6, dpv, dM, J);
+    const float ph[4] = {p[0], p[1], p[2], 1.0f};
+    // J = [[J00, 0, J02], [0, J11, J12]]
+    const float Jc[6] = {J[0], 0.0f, J[1], 0.0f, J[2], J[3]};
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            float v = ph[r] * dpv[k];
+            if (r < 3) v += Jc[k] * dM[r] + Jc[3 + k] * dM[3 + r];
+            t[3 * r + k] = v;
+        }
+    const float* pr = c.proj;
+    float mh0 = pr[0] * p[0] + pr[4] * p[1] + pr[8] * p[2] + pr[12];
+    float mh1 = pr[1] * p[0] + pr[5] * p[1] + pr[9] * p[2] + pr[13];
+    float mw = 1.0f / (proj_w(pr, p) + FDGS_W_EPS);
+    float mul1 = mh0 * mw * mw, mul2 = mh1 * mw * mw;
+    const float dhom[3] = {mw * g_ndc_x, mw * g_ndc_y, -(mul1 * g_ndc_x + mul2 * g_ndc_y)};
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) t[12 + 3 * r + k] = ph[r] * dhom[k];
+    float dm[3] = {0.f, 0.f, 0.f};
+    if (sh) {
+        float dsh[48];
+        sh_bwd(c.D, sh, p, c.campos, clamped, dL_drgb, dsh, dm);
+    }
+    t[24] = -dm[0]; t[25] = -dm[1]; t[26] = -dm[2];
 }
 
 // dL/dSigma (6 unique entries, off-diagonals carry both symmetric halves) -> dL/dscale, dL/dq (q as given)

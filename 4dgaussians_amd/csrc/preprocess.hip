@@ -477,6 +477,97 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(PreBwdArgs a) {
     }
 }
 
+// ---- the camera's gradient (fdgs_camera_grad): dL/d(viewmatrix, projmatrix, campos) summed over the Gaussians --------------------------
+// Runs behind fdgs_raster_bwd on the accumulator that call left.  A kernel of its own, so a frame whose camera asks for no gradient runs
+// preprocess_bwd_kernel untouched; the price is a second read of a live Gaussian's line, position, covariance and SH.
+// Two launches, no float atomics: every workgroup of the first writes one row of CAM_ROW partial sums, one workgroup adds the rows in a
+// fixed order (in double) -- for a given accumulator the result is the same bits every run.
+constexpr int CAM_TERMS = 27;    // gs_math.h camera_terms
+constexpr int CAM_ROW = 32;      // floats per row of partials (128 bytes)
+
+struct CamGradArgs : FrameHead {
+    const float* cov3D; const uint32_t *tiles, *clamped;
+    const float* gacc;           // [P,16] as PreBwdArgs
+    float* partial;              // [gridDim.x][CAM_ROW]
+};
+
+__global__ void __launch_bounds__(256) camera_grad_partial_kernel(CamGradArgs a) {
+    __shared__ float wsum[4][CAM_ROW];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    // the activity test of preprocess_bwd_kernel: tiles and a non-zero line from the blending backward
+    float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0, g2 = g0;
+    bool live = false;
+    if (i < a.P && a.tiles[i] != 0) {
+        const float4* ga = reinterpret_cast<const float4*>(a.gacc + 16 * (size_t)i);
+        g0 = ga[0]; g1 = ga[1]; g2 = ga[2];
+        live = g0.x != 0.f || g0.y != 0.f || g0.z != 0.f || g0.w != 0.f || g1.x != 0.f || g1.y != 0.f || g1.z != 0.f || g1.w != 0.f ||
+               g2.x != 0.f || g2.y != 0.f;
+    }
+    float t[CAM_TERMS];
+#pragma unroll
+    for (int k = 0; k < CAM_TERMS; k++) t[k] = 0.f;
+    // a wave without a live lane (in spatial order: most waves of a dense scene) loads nothing more and skips the reduction
+    if (__any(live)) {
+        if (live) {
+            CamConst c;
+            load_cam(c, a.view, a.proj, a.campos, a.W, a.H, a.tanfovx, a.tanfovy, a.scale_mod, a.D, a.M);
+            float p[3] = {a.means3D[3 * (size_t)i], a.means3D[3 * (size_t)i + 1], a.means3D[3 * (size_t)i + 2]};
+            float c6[6];
+#pragma unroll
+            for (int k = 0; k < 6; k++) c6[k] = a.cov3D[6 * (size_t)i + k];
+            float m2d[2];
+            mean2d_grad_to_ndc(g0.x, g0.y, a.W, a.H, m2d);
+            const float dconic[3] = {g0.z, g0.w, g1.x}, drgb[3] = {g1.z, g1.w, g2.x};
+            camera_terms(c, p, c6, dconic, g2.y, m2d[0], m2d[1], a.shs ? a.shs + (size_t)i * a.M * 3 : nullptr, a.shs ? a.clamped[i] : 0u,
+                         drgb, t);
+        }
+#pragma unroll
+        for (int k = 0; k < CAM_TERMS; k++) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) t[k] += __shfl_xor(t[k], o, 64);
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < CAM_TERMS; k++) wsum[wave][k] = t[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < CAM_ROW) {
+        const int k = threadIdx.x;
+        a.partial[(size_t)blockIdx.x * CAM_ROW + k] = k < CAM_TERMS ? ((wsum[0][k] + wsum[1][k]) + wsum[2][k]) + wsum[3][k] : 0.f;
+    }
+}
+
+// One workgroup: thread (g, k) = (threadIdx.x / 32, threadIdx.x % 32) adds term k of the rows g, g + 8, ... in order, the eight
+// group sums are added in order, and the 27 sums are laid out as the 48 floats of include/fdgs.h.  The rows are added in double: a
+// thread's chain is rows / 8 additions long, and in float its rounding was the largest term of the translation identity's residual
+// (tests/test_gpu_camera_grad.py).  The launch waits on one load per thread at a time (0.038 ms at 1 172 rows).
+__global__ void __launch_bounds__(256) camera_grad_final_kernel(const float* __restrict__ partial, int rows, float* __restrict__ out) {
+    __shared__ double gsum[8][CAM_ROW];
+    __shared__ double total[CAM_ROW];
+    const int g = threadIdx.x >> 5, k = threadIdx.x & 31;
+    double s = 0.0;
+    for (int r = g; r < rows; r += 8) s += (double)partial[(size_t)r * CAM_ROW + k];
+    gsum[g][k] = s;
+    __syncthreads();
+    if (threadIdx.x < CAM_ROW) {
+        double v = gsum[0][k];
+#pragma unroll
+        for (int q = 1; q < 8; q++) v += gsum[q][k];
+        total[k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 48) {
+        const int j = threadIdx.x, r = (j & 15) >> 2, c = j & 3;
+        double v = 0.0;
+        if (j < 16) { if (c < 3) v = total[3 * r + c]; }
+        else if (j < 32) { if (c != 2) v = total[12 + 3 * r + (c == 3 ? 2 : c)]; }
+        else if (j < 35) v = total[24 + (j - 32)];
+        out[j] = (float)v;
+    }
+}
+
 __global__ void __launch_bounds__(256) mark_visible_kernel(int P, const float* __restrict__ means3D,
                                                            const float* __restrict__ view, uint8_t* present) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -669,5 +760,75 @@ extern "C" int fdgs_preprocess_bwd_host(const fdgs_raster_params* p, const uint3
             for (int k = 0; k < 4; k++) dL_drotations[4 * i + k] = dq[k];
         }
     }
+    return FDGS_OK;
+}
+
+// ---- the camera's gradient (include/fdgs.h: fdgs_camera_grad_scratch_bytes, fdgs_camera_grad, fdgs_camera_grad_host) ---------------------
+
+extern "C" int fdgs_camera_grad_scratch_bytes(int P, size_t* bytes) {
+    FDGS_REQUIRE(P >= 0, "bad P");
+    FDGS_REQUIRE(bytes != nullptr, "bytes is NULL");
+    *bytes = (size_t)(P > 0 ? cdiv(P, 256) : 1) * CAM_ROW * sizeof(float);
+    return FDGS_OK;
+}
+
+extern "C" int fdgs_camera_grad(void* stream_, const fdgs_raster_params* p, const void* geom, const float* scratch_acc, void* scratch,
+                                float* out) {
+    int rc = validate_raster_params(p);
+    if (rc) return rc;
+    FDGS_REQUIRE(out != nullptr, "out is NULL");
+    FDGS_REQUIRE(aligned_to(out, 16), "out must be 16-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (p->P == 0) {
+        FDGS_HIP_CHECK(hipMemsetAsync(out, 0, 48 * sizeof(float), stream));
+        return FDGS_OK;
+    }
+    FDGS_REQUIRE(geom && scratch_acc && scratch, "NULL buffer");
+    FDGS_REQUIRE(aligned_to(scratch_acc, 16) && aligned_to(scratch, 16), "scratch_acc and scratch must be 16-byte aligned");
+    GeomLayout gl = geom_layout(p->P);
+    CamGradArgs a{};
+    fill_frame_head(a, p);
+    a.cov3D = at<float>(geom, gl.cov3D); a.tiles = at<uint32_t>(geom, gl.tiles); a.clamped = at<uint32_t>(geom, gl.clamped);
+    a.gacc = scratch_acc; a.partial = static_cast<float*>(scratch);
+    const int rows = cdiv(p->P, 256);
+    { FDGS_TIMED("camera_grad_partial", stream); hipLaunchKernelGGL(camera_grad_partial_kernel, dim3(rows), dim3(256), 0, stream, a); }
+    FDGS_LAUNCH_CHECK("camera_grad_partial", p->debug, stream);
+    { FDGS_TIMED("camera_grad_final", stream); hipLaunchKernelGGL(camera_grad_final_kernel, dim3(1), dim3(256), 0, stream, a.partial, rows, out); }
+    FDGS_LAUNCH_CHECK("camera_grad_final", p->debug, stream);
+    return FDGS_OK;
+}
+
+// Host twin: the loop of fdgs_preprocess_bwd_host around camera_terms, summed in double.
+extern "C" int fdgs_camera_grad_host(const fdgs_raster_params* p, const uint32_t* tiles, const uint32_t* clamped, const float* cov3D,
+                                     const float* d_xy, const float* d_conic, const float* d_rgb, const float* d_depth, double* out) {
+    int rc = validate_raster_params(p);
+    if (rc) return rc;
+    FDGS_REQUIRE(out != nullptr, "out is NULL");
+    FDGS_REQUIRE(p->P == 0 || (tiles && cov3D && d_xy && d_conic && d_rgb), "an array is NULL");
+    FDGS_REQUIRE(p->P == 0 || !p->shs || clamped, "SH inputs need clamped");
+    double sum[CAM_TERMS];
+    for (int k = 0; k < CAM_TERMS; k++) sum[k] = 0.0;
+    CamConst c;
+    load_cam(c, p->viewmatrix, p->projmatrix, p->campos, p->W, p->H, p->tanfovx, p->tanfovy, p->scale_modifier, p->sh_degree, p->sh_coeffs);
+    const int M = p->sh_coeffs;
+    for (size_t i = 0; i < (size_t)p->P; i++) {
+        const float dd = d_depth ? d_depth[i] : 0.f;
+        const float* gxy = d_xy + 2 * i; const float* gco = d_conic + 3 * i; const float* grgb = d_rgb + 3 * i;
+        const bool any_grad = gxy[0] != 0.f || gxy[1] != 0.f || gco[0] != 0.f || gco[1] != 0.f || gco[2] != 0.f || grgb[0] != 0.f ||
+                              grgb[1] != 0.f || grgb[2] != 0.f || dd != 0.f;
+        if (tiles[i] == 0 || !any_grad) continue;
+        float m2d[2], t[CAM_TERMS];
+        mean2d_grad_to_ndc(gxy[0], gxy[1], p->W, p->H, m2d);
+        camera_terms(c, p->means3D + 3 * i, cov3D + 6 * i, gco, dd, m2d[0], m2d[1], p->shs ? p->shs + i * (size_t)M * 3 : nullptr,
+                     p->shs ? clamped[i] : 0u, grgb, t);
+        for (int k = 0; k < CAM_TERMS; k++) sum[k] += (double)t[k];
+    }
+    for (int j = 0; j < 48; j++) out[j] = 0.0;
+    for (int r = 0; r < 4; r++)
+        for (int k = 0; k < 3; k++) {
+            out[4 * r + k] = sum[3 * r + k];
+            out[16 + 4 * r + (k == 2 ? 3 : k)] = sum[12 + 3 * r + k];
+        }
+    for (int k = 0; k < 3; k++) out[32 + k] = sum[24 + k];
     return FDGS_OK;
 }

@@ -298,8 +298,34 @@ def fill_raster_grads(state, grad_color, grad_depth, d_means2D, epilogue=None):
     return g, acc
 
 
-def rasterize_backward(state, grad_color, grad_depth=None):
-    """Backward of rasterize_forward. Returns dict of gradients (None where the input was absent)."""
+def camera_wants_grad(settings):
+    """A frame asks for the camera's gradient when grad mode is on and viewmatrix, projmatrix or campos of its settings is a tensor that
+    requires grad (a pose being refined, fdgs.camera.PoseDelta; tracking against a frozen model).  Read where the frame is built: inside
+    autograd.Function.forward grad mode is always off."""
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                           for t in (settings.viewmatrix, settings.projmatrix, settings.campos))
+
+
+def camera_gradients(state, acc):
+    """fdgs_camera_grad behind fdgs_raster_bwd of `state`, on the accumulator `acc` that call used -> [48] floats: dL/dviewmatrix [0,16),
+    dL/dprojmatrix [16,32), dL/dcampos [32,35) (include/fdgs.h).  Two launches, no atomics."""
+    L = _lib.lib()
+    p, dev = state.params, state.geom.device
+    scratch = torch.empty(_bytes(L, "camera_grad_scratch", p.P), dtype=torch.uint8, device=dev)
+    out = torch.empty(48, device=dev)
+    check(L.fdgs_camera_grad(stream_ptr(), p, ptr(state.geom), ptr(acc), ptr(scratch), ptr(out)))
+    return out
+
+
+def split_camera_gradients(out48, viewmatrix, projmatrix, campos):
+    """The 48 floats of camera_gradients as gradients shaped (and typed, and placed) like the three camera tensors."""
+    like = lambda g, t: None if not isinstance(t, torch.Tensor) else g.reshape(t.shape).to(device=t.device, dtype=t.dtype)
+    return like(out48[:16], viewmatrix), like(out48[16:32], projmatrix), like(out48[32:35], campos)
+
+
+def rasterize_backward(state, grad_color, grad_depth=None, camera=False):
+    """Backward of rasterize_forward. Returns dict of gradients (None where the input was absent).  `camera`: also the camera's gradient,
+    as `viewmatrix` [4,4], `projmatrix` [4,4] and `campos` [3] (fdgs_camera_grad on the same accumulator, behind fdgs_raster_bwd)."""
     L = _lib.lib()
     p = state.params
     means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp = state.keep[:7]
@@ -315,6 +341,9 @@ def rasterize_backward(state, grad_color, grad_depth=None):
     g.dL_dmeans3D, g.dL_dopacity, g.dL_dcolors, g.dL_dcov3D = ptr(out["means3D"]), ptr(out["opacities"]), ptr(out["colors"]), ptr(out["cov3D"])
     g.dL_dsh, g.dL_dscales, g.dL_drotations = ptr(out["shs"]), ptr(out["scales"]), ptr(out["rotations"])
     check(L.fdgs_raster_bwd(stream_ptr(), p, ptr(state.geom), ptr(state.binning), ptr(state.img), state.capacity, g))
+    if camera:
+        c = out["camera"] = camera_gradients(state, scratch)       # (the call's 48 floats; the three below are views of it)
+        out.update(viewmatrix=c[:16].reshape(4, 4), projmatrix=c[16:32].reshape(4, 4), campos=c[32:35])
     return out
 
 
@@ -348,7 +377,45 @@ class _RasterizeGaussians(torch.autograd.Function):
                 g["cov3D"] if had_cov else None, None, None)
 
 
+class _RasterizeGaussiansCamera(torch.autograd.Function):
+    """_RasterizeGaussians for a frame whose camera asks for a gradient (camera_wants_grad): viewmatrix, projmatrix and campos of the
+    settings are inputs as well, and their gradients come from fdgs_camera_grad behind the same fdgs_raster_bwd.  A sibling, so that the
+    frames that do not ask run the node and the C calls they always ran.  The Gaussians may all be detached (tracking)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix, campos,
+                raster_settings):
+        color, radii, depth, state = rasterize_forward(raster_settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                                       expect_backward=True)
+        ctx.state = state
+        ctx.had = (sh is not None and sh.numel() > 0, colors_precomp is not None and colors_precomp.numel() > 0,
+                   scales is not None and scales.numel() > 0, cov3Ds_precomp is not None and cov3Ds_precomp.numel() > 0)
+        ctx.shapes = (opacities.shape, None if sh is None else sh.shape)
+        ctx.cam = (viewmatrix, projmatrix, campos)        # (shape / dtype / device of the gradients to return; inputs of this node anyway)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return color, radii, depth
+
+    @staticmethod
+    def backward(ctx, grad_color, grad_radii, grad_depth):
+        if grad_color is None:
+            if grad_depth is None:
+                return (None,) * 12
+            grad_color = torch.zeros(3, ctx.state.params.H, ctx.state.params.W, device=grad_depth.device)
+        g = rasterize_backward(ctx.state, grad_color, grad_depth, camera=True)
+        had_sh, had_col, had_scale, had_cov = ctx.had
+        op_shape, sh_shape = ctx.shapes
+        cam = split_camera_gradients(g["camera"], *ctx.cam)
+        return (g["means3D"], g["means2D"], g["shs"].reshape(sh_shape) if had_sh else None, g["colors"] if had_col else None,
+                g["opacities"].reshape(op_shape), g["scales"] if had_scale else None, g["rotations"] if had_scale else None,
+                g["cov3D"] if had_cov else None, *cam, None)
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+    if camera_wants_grad(raster_settings):
+        rs = raster_settings
+        return _RasterizeGaussiansCamera.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                               rs.viewmatrix, rs.projmatrix, rs.campos, rs)
     # (grad mode is read HERE: inside autograd.Function.forward it is always off and needs_input_grad stays True under torch.no_grad())
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                      raster_settings, torch.is_grad_enabled())

@@ -95,12 +95,14 @@ def _fill_epilogue(st, b, assign):
     return epi
 
 
-def _fused_backward(states, saved, grad_colors, grad_depths, **prepare):
+def _fused_backward(states, saved, grad_colors, grad_depths, camera=None, **prepare):
     """The backward of the fused fine stage for the views of one autograd node: states = [(deformation state, raster state)], saved = their
     (o_sc, o_rot, o_op) in a row, grad_colors / grad_depths = the per-view image gradients (or None), `prepare` goes to backward_prepare.
     Last view first (its saved activations, lists and records are the ones still partly resident in the 256 MB Infinity Cache), per view: the
     rasterizer backward, whose epilogue writes into the ONE gradient arena (the first processed view assigns the identity paths, later ones
-    accumulate), then that view's deformation backward -- same output pointers and scratch (stream-ordered reuse), its own saved activations."""
+    accumulate), then that view's deformation backward -- same output pointers and scratch (stream-ordered reuse), its own saved activations.
+    `camera`: a list that receives, per processed view, the 48 floats of fdgs_camera_grad, run behind that view's fdgs_raster_bwd on its
+    accumulator (frames whose camera asks for a gradient: _FusedRenderCameraFunction)."""
     L, stream = _lib.lib(), _lib.stream_ptr()
     st0 = states[0][0]
     b = _deformation.backward_prepare(st0, saved[0], saved[1], saved[2], identity_assigned=EPILOGUE_ASSIGN, **prepare)
@@ -115,6 +117,8 @@ def _fused_backward(states, saved, grad_colors, grad_depths, **prepare):
         epi = _fill_epilogue(st, b, EPILOGUE_ASSIGN and k_ == 0)
         g, acc = _rasterizer.fill_raster_grads(rstate, gc, gd, gm, epi)      # (acc: zero-filled by the blending forward of this frame, no fill launch here)
         _lib.check(L.fdgs_raster_bwd(stream, p, _lib.ptr(rstate.geom), _lib.ptr(rstate.binning), _lib.ptr(rstate.img), rstate.capacity, g))
+        if camera is not None:
+            camera.append(_rasterizer.camera_gradients(rstate, acc))
         b.g.out_scales, b.g.out_rotations, b.g.out_opacity = _lib.ptr(saved[3 * v]), _lib.ptr(saved[3 * v + 1]), _lib.ptr(saved[3 * v + 2])
         b.g.rot_norm, b.g.saved = _lib.ptr(st.o_norm), _lib.ptr(st.saved_act)
         b.g.packed_rows_ready = epi.tile_flags + 1
@@ -148,6 +152,36 @@ class _FusedRenderFunction(torch.autograd.Function):
         g_means2D, grads = _fused_backward([(st, ctx.rstate)], ctx.saved_tensors, None if grad_color is None else (grad_color,),
                                            None if grad_depth is None else (grad_depth,), zero_by_epilogue=EPILOGUE_ASSIGN)
         return (None, None, None, *g_means2D) + grads[:6] + grads[7:]       # (grads[6]: the time tensor, no input here)
+
+
+class _FusedRenderCameraFunction(torch.autograd.Function):
+    """_FusedRenderFunction for a frame whose camera asks for a gradient (rasterizer.camera_wants_grad): viewmatrix, projmatrix and campos of
+    the settings are inputs too and get the gradients of fdgs_camera_grad, run behind the same fdgs_raster_bwd.  A sibling, so that every
+    other frame runs the node and the C calls it always ran."""
+
+    @staticmethod
+    def forward(ctx, cfg, t_scalar, raster_settings, viewmatrix, projmatrix, campos, means2D, xyz, scales, rotations, opacity, sh_a, sh_b, aabb,
+                *rest):
+        st = _deformation.forward_impl(cfg, t_scalar, xyz, scales, rotations, opacity, sh_a, sh_b, None, aabb, rest, True)
+        color, radii, depth, rstate = _rasterizer.rasterize_forward(raster_settings, st.o_xyz, st.o_sh, None, st.o_op, st.o_sc, st.o_rot, None,
+                                                                    expect_backward=True)
+        ctx.st, ctx.rstate, ctx.cam = st, rstate, (viewmatrix, projmatrix, campos)
+        ctx.save_for_backward(st.o_sc, st.o_rot, st.o_op)
+        st.o_xyz = st.o_sc = st.o_rot = st.o_op = st.o_sh = None
+        vis = rstate.visibility
+        ctx.mark_non_differentiable(radii, vis)
+        ctx.set_materialize_grads(False)
+        return color, radii, depth, vis
+
+    @staticmethod
+    def backward(ctx, grad_color, grad_radii, grad_depth, grad_vis=None):
+        st = ctx.st
+        if grad_color is None and grad_depth is None:
+            return (None,) * (14 + len(st.plane_shapes) + len(st.keep[0][8]))
+        cam = []
+        g_means2D, grads = _fused_backward([(st, ctx.rstate)], ctx.saved_tensors, None if grad_color is None else (grad_color,),
+                                           None if grad_depth is None else (grad_depth,), camera=cam, zero_by_epilogue=EPILOGUE_ASSIGN)
+        return (None, None, None, *_rasterizer.split_camera_gradients(cam[0], *ctx.cam), *g_means2D) + grads[:6] + grads[7:]
 
 
 class _FusedRenderViewsFunction(torch.autograd.Function):
@@ -253,7 +287,11 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
             and not pipe.convert_SHs_python and isinstance(pc._deformation, _deformation.deform_network)):
         # deformation + rasterizer as one autograd node (see _FusedRenderFunction)
         cfg, perm, ins, net_ins = _fine_stage(pc, (screenspace_points,) if torch.is_grad_enabled() else ())
-        if cfg["grad"]:
+        if cfg["grad"] and _rasterizer.camera_wants_grad(raster_settings):
+            rs = raster_settings
+            rendered_image, radii, depth, vis = _FusedRenderCameraFunction.apply(cfg, frame_time, rs, rs.viewmatrix, rs.projmatrix, rs.campos,
+                                                                                 *ins, *net_ins)
+        elif cfg["grad"]:
             rendered_image, radii, depth, vis = _FusedRenderFunction.apply(cfg, frame_time, raster_settings, *ins, *net_ins)
         else:
             # no graph will be recorded (render.py:57-70, evaluation): the two stages called directly -- autograd.Function.apply costs

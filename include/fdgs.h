@@ -222,6 +222,25 @@ int fdgs_preprocess_bwd_host(const fdgs_raster_params* p, const uint32_t* tiles,
                              float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
                              float* dL_dcov3D);
 
+/* The camera's gradient: dL/d(viewmatrix, projmatrix, campos) of the frame whose fdgs_raster_bwd has just run -- the three tensors every
+ * other call reads as constants.  Each visible Gaussian's share comes from the sums its chain rule already takes (csrc/gs_math.h
+ * camera_terms); these calls add the shares up.  Row-vector convention, row-major matrices, entry [4*r + c].
+ *   out[48], ASSIGNED (not accumulated):  [0,16) dL/dviewmatrix (column 3 exactly 0)   [16,32) dL/dprojmatrix (column 2 exactly 0)
+ *                                         [32,35) dL/dcampos (0 with colors_precomp)    [35,48) zeros
+ *   fdgs_camera_grad_scratch_bytes: size of `scratch` for P Gaussians (one 128-byte row of partial sums per 256 Gaussians).
+ *   fdgs_camera_grad: call it after fdgs_raster_bwd of the same state (same p, same geom) with the scratch_acc that call used --
+ *     fdgs_raster_bwd only reads the accumulator once the blending backward has filled it, so it is intact.  Reads tiles, clamped and cov3D
+ *     from geom.  Two launches (per-workgroup partial rows, then one workgroup adds the rows in a fixed order) and no float atomics: for a
+ *     given scratch_acc the 48 floats are the same bits every run.  scratch_acc, scratch and out are device pointers, 16-byte aligned.
+ *     P == 0 writes zeros (geom, scratch_acc and scratch may then be NULL).
+ *   fdgs_camera_grad_host: the host twin -- the loop of fdgs_preprocess_bwd_host, with that call's inputs (host pointers, d_depth NULL:
+ *     zeros), around the same function, summed in double.  A difference to the device is the device's float summation and contraction. */
+int fdgs_camera_grad_scratch_bytes(int P, size_t* bytes);
+int fdgs_camera_grad(void* stream, const fdgs_raster_params* p, const void* geom, const float* scratch_acc, void* scratch,
+                     float* out /* 48 floats, 16-byte aligned */);
+int fdgs_camera_grad_host(const fdgs_raster_params* p, const uint32_t* tiles, const uint32_t* clamped, const float* cov3D,
+                          const float* d_xy, const float* d_conic, const float* d_rgb, const float* d_depth, double* out /* 48 */);
+
 /* Test/diagnostic access to geom fields (device pointers into `geom`):
  * 0 depth f32[P]; 1 recA float4[P] (x,y,conic.xx,conic.xy); 2 recB float4[P] (conic.yy,opacity,depth,0);
  * 3 recC float4[P] (r,g,b,0); 4 cov3D f32[P,6]; 5 tiles_touched u32[P]; 6 clamped u32[P] (bit c = channel c);
