@@ -317,22 +317,13 @@ __global__ void __launch_bounds__(256) render_fwd_kernel(RenderArgs a) {
     }
 }
 
+#include "blend_replay.h"              // the replay walk: what the four kernels below share (ReplayArgs, replay_pixel ... replay_row)
+
 // ---- the pick pass: which Gaussian a pixel shows, and the depth at which it turns opaque ----------------------------------------------
-// One more walk over the lists of a FINISHED frame, front to back, up to each pixel's n_contrib, taking the decisions render_fwd_kernel
-// took: the same expressions for the power, alpha, w = alpha * T and T, so w has the bits of the forward's w (the forward contracts only
-// its colour sums, which do not exist here; this kernel is compiled without contraction so that A += alpha * T stays a product and a sum,
-// the float32 running sum a blended colour channel of ones accumulates).  The layout is the forward's: one workgroup per tile in the
-// forward's own tile order (read, not rebuilt), 256 entries staged per round through LDS -- recA, recB and this time the ids, recC is
-// not read --, ids two rounds ahead and records one round ahead in registers.  Per lane: T, A, the largest w and its id, the id and depth
-// of the entry at which A reached alpha_cut.  Nothing of the frame is written: no atomics, the four images are the only stores.
-struct PickArgs : BlendHead {
-    const uint32_t* tile_todo;               // per tile: max n_contrib, the forward's walk length
-    const uint2* ranges; const uint32_t* pair_gid;
-    const float4 *recA, *recB, *recC;
-    const float* bg;
-    const float* final_T; const uint32_t* n_contrib;
-    uint32_t R; int P;                       // what the lists were laid out for: fences for a stale img
-    int empty;                               // 1: no Gaussians or no pairs, every pixel gets -1 / +0 and nothing of the frame is read
+// A replay walk (blend_replay.h) that stages the ids beside recA and recB.  A += w is compiled without contraction: a product and a sum,
+// the float32 running sum a blended colour channel of ones accumulates.  Per lane: T, A, the largest w and its id, the id and depth of the
+// entry at which A reached alpha_cut.  No atomics, the four images are the only stores.  On an empty frame every pixel gets -1 / +0.
+struct PickArgs : ReplayArgs {
     float alpha_cut;
     const int32_t* row_map;                  // opt [P]: the id written for Gaussian g
     int32_t* pick_id; float* pick_weight; int32_t* surface_id; float* surface_depth;      // each opt
@@ -340,81 +331,51 @@ struct PickArgs : BlendHead {
 
 __global__ void __launch_bounds__(256) render_pick_kernel(PickArgs a) {
 #pragma clang fp contract(off)
-    const int tile = a.empty ? unit_of_block(blockIdx.x, a.gx, a.gy, 1, a.bh) : unit_lookup(a.order, a.per_xcd, blockIdx.x, a.gx, a.gy, 1, a.bh);
-    if (tile < 0 || tile >= a.gx * a.gy) return;
+    const ReplayPixel px = replay_pixel<true>(a);
+    if (px.tile < 0) return;
     __shared__ float4 sA[256], sB[256];
     __shared__ uint32_t sG[256];
     const int t = threadIdx.x;
-    const int x = (tile % a.gx) * TILE + (t & 15), y = (tile / a.gx) * TILE + (t >> 4);
-    const bool inside = x < a.W && y < a.H;
-    const float pxf = (float)x, pyf = (float)y;
-    const size_t pix = (size_t)y * a.W + x;
-    uint2 range = make_uint2(0u, 0u);
-    uint32_t walk = 0u, own = 0u;
-    if (!a.empty) {
-        range = a.ranges[tile];
-        range.y = range.y < a.R ? range.y : a.R;
-        range.x = range.x < range.y ? range.x : range.y;
-        walk = a.tile_todo[tile];
-        own = inside ? a.n_contrib[pix] : 0u;
-    }
-    const int n_list = (int)(range.y - range.x);
-    const int todo = walk < (uint32_t)n_list ? (int)walk : n_list;           // the tile's walk length ...
-    const int mine = own < (uint32_t)n_list ? (int)own : n_list;            // ... and this lane's, both clamped to the list
-    const int rounds = (todo + 255) / 256;
+    const ReplayLengths len = replay_lengths<true>(a, px.tile, px.own);
     float T = 1.0f, A = 0.0f, best_w = 0.0f, s_depth = 0.0f;
     uint32_t best_g = 0xFFFFFFFFu, s_g = 0xFFFFFFFFu;
     int seen = 0;                            // entries of the list this lane has passed
-    auto gid_of = [&](int r) -> uint32_t {
-        const int e = r * 256 + t;
-        return a.pair_gid[range.x + (e < n_list ? e : n_list - 1)];
-    };
     uint32_t g_cur = 0u, g_nxt = 0u;
     float4 rA, rB;
-    if (rounds > 0) {
-        g_cur = gid_of(0);
-        if (rounds > 1) g_nxt = gid_of(1);
+    if (len.rounds > 0) {
+        g_cur = replay_gid(a, len, 0);
+        if (len.rounds > 1) g_nxt = replay_gid(a, len, 1);
         rA = a.recA[g_cur]; rB = a.recB[g_cur];
     }
-    for (int r = 0; r < rounds; r++) {
-        if (__syncthreads_count(seen >= mine) == 256) break;
+    for (int r = 0; r < len.rounds; r++) {
+        if (__syncthreads_count(seen >= len.mine) == 256) break;
         sA[t] = rA; sB[t] = rB; sG[t] = g_cur;
         __syncthreads();
-        if (r + 1 < rounds) { g_cur = g_nxt; rA = a.recA[g_cur]; rB = a.recB[g_cur]; }
-        if (r + 2 < rounds) g_nxt = gid_of(r + 2);
-        const int rem = mine - seen;
+        if (r + 1 < len.rounds) { g_cur = g_nxt; rA = a.recA[g_cur]; rB = a.recB[g_cur]; }
+        if (r + 2 < len.rounds) g_nxt = replay_gid(a, len, r + 2);
+        const int rem = len.mine - seen;
         const int lim = rem < 256 ? rem : 256;
         for (int j = 0; j < lim; j++) {
-            const float4 Aj = sA[j];
             const float4 B = sB[j];
-            const float dx = Aj.x - pxf, dy = Aj.y - pyf;
-            const float power = blend_power(blend_power_xx(Aj.z, dx), blend_power_xy(Aj.w, dx), B.x, dy);
-            if (power > 0.0f) continue;
-            const float alpha = fminf(FDGS_ALPHA_MAX, B.y * __expf(power));
-            if (alpha < FDGS_ALPHA_MIN) continue;
-            const float w = alpha * T;
-            A = A + w;
-            if (w > best_w) { best_w = w; best_g = sG[j]; }                  // (strictly: on a tie the entry in front stays)
-            if (s_g == 0xFFFFFFFFu && A >= a.alpha_cut) { s_g = sG[j]; s_depth = B.z; }
-            T = T * (1.0f - alpha);
+            replay_hit(sA[j], B, px.pxf, px.pyf, T, [&](float w, float T_behind) {
+                A = A + w;
+                if (w > best_w) { best_w = w; best_g = sG[j]; }              // (strictly: on a tie the entry in front stays)
+                if (s_g == 0xFFFFFFFFu && A >= a.alpha_cut) { s_g = sG[j]; s_depth = B.z; }
+                T = T_behind;
+            });
         }
         seen += 256;
     }
-    if (inside) {
-        auto id_of = [&](uint32_t g) -> int32_t {
-            if (g >= (uint32_t)a.P) return -1;
-            return a.row_map ? a.row_map[g] : (int32_t)g;
-        };
-        if (a.pick_id) a.pick_id[pix] = id_of(best_g);
-        if (a.pick_weight) a.pick_weight[pix] = best_w;
-        if (a.surface_id) a.surface_id[pix] = id_of(s_g);
-        if (a.surface_depth) a.surface_depth[pix] = s_depth;
+    if (px.inside) {
+        if (a.pick_id) a.pick_id[px.pix] = replay_row(a, best_g, a.row_map, 0xFFFFFFFFu);      // (no bound on the caller's ids)
+        if (a.pick_weight) a.pick_weight[px.pix] = best_w;
+        if (a.surface_id) a.surface_id[px.pix] = replay_row(a, s_g, a.row_map, 0xFFFFFFFFu);
+        if (a.surface_depth) a.surface_depth[px.pix] = s_depth;
     }
 }
 
 // ---- the feature pass: C per-row channels blended in one walk ---------------------------------------------------------------------------
-// The pick pass's walk once more (its layout, staging pipeline, tile order, clamps and expressions, compiled without contraction: w has
-// the bits of the forward's w), with per-row VALUES in place of the colour record: channel c of a pixel is the sum over its contributors
+// A replay walk (blend_replay.h) with per-row VALUES in place of the colour record: channel c of a pixel is the sum over its contributors
 // of values[row, c] * w, accumulated in list order as ONE explicit fused multiply-add per entry -- what the forward's `C0 += Cc.x * w`
 // is compiled to (render_fwd_kernel is built with contraction) --, so a channel has the bits fdgs_render_fwd would blend for it over a zero
 // background, and A = A + w is the pick pass's float32 running sum (the blend of a channel of ones: 1 * w is exact).
@@ -424,20 +385,13 @@ __global__ void __launch_bounds__(256) render_pick_kernel(PickArgs a) {
 // the same four float4 (broadcast reads).  The chunk size was measured (tools/features_timing.py): 8 keeps the pick pass's
 // occupancy (54 VGPRs, 16.6 KB of LDS) and is faster up to C = 8 (config 4: 0.121 against 0.152 ms at C = 3), 16 (78 VGPRs, 24.8 KB: six
 // waves per SIMD) pays the walk half as often and is faster from C = 9 on (0.161 against 0.215 ms at C = 16, 0.286 against 0.394 at C = 32).
-// recC is not read.  Nothing of the frame is written: no atomics, the planes are the only stores.
+// No atomics, the planes are the only stores.  On an empty frame every pixel gets +0.
 #ifndef FDGS_FEAT_CH
 #define FDGS_FEAT_CH 16                      // (8 at build time is the form it was measured against; a multiple of 4)
 #endif
 constexpr int FEAT_CH = FDGS_FEAT_CH, FEAT_V4 = FEAT_CH / 4;
 static_assert(FEAT_CH % 4 == 0 && FEAT_CH >= 4, "whole float4 records");
-struct FeatArgs : BlendHead {
-    const uint32_t* tile_todo;               // per tile: max n_contrib, the forward's walk length
-    const uint2* ranges; const uint32_t* pair_gid;
-    const float4 *recA, *recB, *recC;
-    const float* bg;
-    const float* final_T; const uint32_t* n_contrib;
-    uint32_t R; int P;                       // what the lists were laid out for: fences for a stale img
-    int empty;                               // 1: no Gaussians or no pairs, every pixel gets +0 and nothing of the frame is read
+struct FeatArgs : ReplayArgs {
     int C; const float* values; int value_stride; int rows;
     const int32_t* row_map;                  // opt [P]: the row of `values` Gaussian g takes
     float min_alpha;                         // < 0: raw sums; else F / A where A > min_alpha, 0 elsewhere
@@ -447,46 +401,26 @@ struct FeatArgs : BlendHead {
 
 __global__ void __launch_bounds__(256) render_features_kernel(FeatArgs a) {
 #pragma clang fp contract(off)
-    const int tile = a.empty ? unit_of_block(blockIdx.x, a.gx, a.gy, 1, a.bh) : unit_lookup(a.order, a.per_xcd, blockIdx.x, a.gx, a.gy, 1, a.bh);
-    if (tile < 0 || tile >= a.gx * a.gy) return;
+    const ReplayPixel px = replay_pixel<true>(a);
+    if (px.tile < 0) return;
     __shared__ float4 sA[256], sB[256], sV[FEAT_V4][256];
     const int t = threadIdx.x;
     const int c0 = (int)blockIdx.y * FEAT_CH;                                // this chunk's first channel
     const int nch = a.C - c0 < FEAT_CH ? a.C - c0 : FEAT_CH;                 // ... and how many of its sixteen exist (>= 1: the grid)
-    const int x = (tile % a.gx) * TILE + (t & 15), y = (tile / a.gx) * TILE + (t >> 4);
-    const bool inside = x < a.W && y < a.H;
-    const float pxf = (float)x, pyf = (float)y;
-    const size_t pix = (size_t)y * a.W + x, hw = (size_t)a.H * a.W;
-    uint2 range = make_uint2(0u, 0u);
-    uint32_t walk = 0u, own = 0u;
-    if (!a.empty) {
-        range = a.ranges[tile];
-        range.y = range.y < a.R ? range.y : a.R;
-        range.x = range.x < range.y ? range.x : range.y;
-        walk = a.tile_todo[tile];
-        own = inside ? a.n_contrib[pix] : 0u;
-    }
-    const int n_list = (int)(range.y - range.x);
-    const int todo = walk < (uint32_t)n_list ? (int)walk : n_list;           // the tile's walk length, clamped to the list ...
-    const int mine = own < (uint32_t)todo ? (int)own : todo;                // ... and this lane's, clamped to the tile's
-    const int rounds = (todo + 255) / 256;
+    const size_t hw = (size_t)a.H * a.W;
+    const ReplayLengths len = replay_lengths<true>(a, px.tile, px.own);
     float T = 1.0f, A = 0.0f;
     float F[FEAT_CH];
 #pragma unroll
     for (int k = 0; k < FEAT_CH; k++) F[k] = 0.0f;
     int seen = 0;                            // entries of the list this lane has passed
-    auto gid_of = [&](int r) -> uint32_t {
-        const int e = r * 256 + t;
-        return a.pair_gid[range.x + (e < n_list ? e : n_list - 1)];
-    };
     // the values of Gaussian g in this chunk: 16-byte loads where the chunk is whole and its address allows them (values itself
     // is only 4-byte aligned: a row slice of a wider array), else one load per channel that exists
     auto values_of = [&](uint32_t g, float4 (&v)[FEAT_V4]) {
 #pragma unroll
         for (int i = 0; i < FEAT_V4; i++) v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (g >= (uint32_t)a.P) return;
-        const uint32_t row = a.row_map ? (uint32_t)a.row_map[g] : g;
-        if (row >= (uint32_t)a.rows) return;                                 // (a -1 of the map is >= rows as well)
+        const int32_t row = replay_row(a, g, a.row_map, (uint32_t)a.rows);
+        if (row < 0) return;
         const float* src = a.values + (size_t)row * (size_t)a.value_stride + c0;
         if (nch == FEAT_CH && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
 #pragma unroll
@@ -501,50 +435,44 @@ __global__ void __launch_bounds__(256) render_features_kernel(FeatArgs a) {
     };
     uint32_t g_cur = 0u, g_nxt = 0u;
     float4 rA, rB, rV[FEAT_V4];
-    if (rounds > 0) {
-        g_cur = gid_of(0);
-        if (rounds > 1) g_nxt = gid_of(1);
+    if (len.rounds > 0) {
+        g_cur = replay_gid(a, len, 0);
+        if (len.rounds > 1) g_nxt = replay_gid(a, len, 1);
         rA = a.recA[g_cur]; rB = a.recB[g_cur]; values_of(g_cur, rV);
     }
-    for (int r = 0; r < rounds; r++) {
-        if (__syncthreads_count(seen >= mine) == 256) break;
+    for (int r = 0; r < len.rounds; r++) {
+        if (__syncthreads_count(seen >= len.mine) == 256) break;
         sA[t] = rA; sB[t] = rB;
 #pragma unroll
         for (int i = 0; i < FEAT_V4; i++) sV[i][t] = rV[i];
         __syncthreads();
-        if (r + 1 < rounds) { g_cur = g_nxt; rA = a.recA[g_cur]; rB = a.recB[g_cur]; values_of(g_cur, rV); }
-        if (r + 2 < rounds) g_nxt = gid_of(r + 2);
-        const int rem = mine - seen;
+        if (r + 1 < len.rounds) { g_cur = g_nxt; rA = a.recA[g_cur]; rB = a.recB[g_cur]; values_of(g_cur, rV); }
+        if (r + 2 < len.rounds) g_nxt = replay_gid(a, len, r + 2);
+        const int rem = len.mine - seen;
         const int lim = rem < 256 ? rem : 256;
         for (int j = 0; j < lim; j++) {
-            const float4 Aj = sA[j];
-            const float4 B = sB[j];
-            const float dx = Aj.x - pxf, dy = Aj.y - pyf;
-            const float power = blend_power(blend_power_xx(Aj.z, dx), blend_power_xy(Aj.w, dx), B.x, dy);
-            if (power > 0.0f) continue;
-            const float alpha = fminf(FDGS_ALPHA_MAX, B.y * __expf(power));
-            if (alpha < FDGS_ALPHA_MIN) continue;
-            const float w = alpha * T;
-            A = A + w;
+            replay_hit(sA[j], sB[j], px.pxf, px.pyf, T, [&](float w, float T_behind) {
+                A = A + w;
+                T = T_behind;
 #pragma unroll
-            for (int i = 0; i < FEAT_V4; i++) {
-                const float4 V = sV[i][j];
-                F[4 * i] = __builtin_fmaf(V.x, w, F[4 * i]); F[4 * i + 1] = __builtin_fmaf(V.y, w, F[4 * i + 1]);
-                F[4 * i + 2] = __builtin_fmaf(V.z, w, F[4 * i + 2]); F[4 * i + 3] = __builtin_fmaf(V.w, w, F[4 * i + 3]);
-            }
-            T = T * (1.0f - alpha);
+                for (int i = 0; i < FEAT_V4; i++) {
+                    const float4 V = sV[i][j];
+                    F[4 * i] = __builtin_fmaf(V.x, w, F[4 * i]); F[4 * i + 1] = __builtin_fmaf(V.y, w, F[4 * i + 1]);
+                    F[4 * i + 2] = __builtin_fmaf(V.z, w, F[4 * i + 2]); F[4 * i + 3] = __builtin_fmaf(V.w, w, F[4 * i + 3]);
+                }
+            });
         }
         seen += 256;
     }
-    if (inside) {
+    if (px.inside) {
         const bool normalize = a.min_alpha >= 0.0f;
         const bool ok = A > a.min_alpha;                                     // (a NaN A: false)
 #pragma unroll
         for (int k = 0; k < FEAT_CH; k++) {
             const float q = F[k] / A;                                        // (IEEE division, as fdgs_motion_resolve's)
-            if (k < nch) a.features[(size_t)(c0 + k) * hw + pix] = normalize ? (ok ? q : 0.0f) : F[k];
+            if (k < nch) a.features[(size_t)(c0 + k) * hw + px.pix] = normalize ? (ok ? q : 0.0f) : F[k];
         }
-        if (a.alpha && blockIdx.y == 0) a.alpha[pix] = A;
+        if (a.alpha && blockIdx.y == 0) a.alpha[px.pix] = A;
     }
 }
 
@@ -604,29 +532,22 @@ __device__ __forceinline__ uint32_t wave_allmax_u(uint32_t v) {
 }
 
 // ---- the contribution pass: how much every Gaussian adds to the image ------------------------------------------------------------------
-// The pick pass's walk once more (its layout, staging pipeline, tile order and expressions, compiled without contraction: w has the bits of
-// the forward's w), but what leaves the kernel is per GAUSSIAN, not per pixel: the sum and the maximum of v = w * pixel_weight over the
-// pixels, the number of pixels with v > 0 and the number of tiles that hold one.  That is the blending backward's shape with three values
-// per hit in place of nine: for a staged entry a wave in which no lane has v > 0 does nothing; otherwise it finishes sum, maximum and
-// count over its 64 lanes in registers (DPP inside the rows, permlane swaps across them, a ballot's popcount) and lane 0 leaves them
-// in the wave's own LDS slot sAcc[entry][wave] with ONE plain 16-byte store (no LDS atomics: ds_add_f32 sustains 0.33 lanes/clk/CU).  After the
-// round the workgroup adds the four slots of every entry and issues at most ONE atomic per word of the Gaussian's 16-byte record and
-// (tile, entry): four neighbouring lanes own the four words of one record -- f32 add, u32 max on the float's bits (v >= +0: the
-// unsigned order of the bits is the order of the values), u32 add, u32 add of 1 -- so one wave's atomics of a pass cover 16 whole
-// records.  (FDGS_CONTRIB_FLUSH_LANES = 1 at build time is the form it was measured against: one lane per record, four atomic
+// A replay walk (blend_replay.h) that stages the ids, but what leaves the kernel is per GAUSSIAN, not per pixel: the sum and the maximum
+// of v = w * pixel_weight over the pixels, the number of pixels with v > 0 and the number of tiles that hold one.  That is the blending
+// backward's shape with three values per hit in place of nine: for a staged entry a wave in which no lane has v > 0 does nothing; otherwise
+// it finishes sum, maximum and count over its 64 lanes in registers (DPP inside the rows, permlane swaps across them, a ballot's popcount)
+// and lane 0 leaves them in the wave's own LDS slot sAcc[entry][wave] with ONE plain 16-byte store (no LDS atomics: ds_add_f32 sustains
+// 0.33 lanes/clk/CU).  After the round the workgroup adds the four slots of every entry and issues at most ONE atomic per word of the
+// Gaussian's 16-byte record and (tile, entry): four neighbouring lanes own the four words of one record -- f32 add, u32 max on the float's
+// bits (v >= +0: the unsigned order of the bits is the order of the values), u32 add, u32 add of 1 -- so one wave's atomics of a pass cover
+// 16 whole records.  (FDGS_CONTRIB_FLUSH_LANES = 1 at build time is the form it was measured against: one lane per record, four atomic
 // instructions, each touching one word of 64 different records -- the same kernel time within 1 %, 0.212 against 0.213 ms on config 4:
-// the flush is not where the time goes, the per-entry reductions are)  The walk loop runs to the WAVE's longest n_contrib so that every lane
-// takes part in the reductions; a lane past its own end contributes v = 0.  Nothing of the frame is written.
+// the flush is not where the time goes, the per-entry reductions are)  The walk loop runs to the WAVE's longest n_contrib so
+// that every lane takes part in the reductions; a lane past its own end contributes v = 0.  Never launched on an empty frame.
 #ifndef FDGS_CONTRIB_FLUSH_LANES
 #define FDGS_CONTRIB_FLUSH_LANES 4
 #endif
-struct ContribArgs : BlendHead {
-    const uint32_t* tile_todo;               // per tile: max n_contrib, the forward's walk length
-    const uint2* ranges; const uint32_t* pair_gid;
-    const float4 *recA, *recB, *recC;
-    const float* bg;
-    const float* final_T; const uint32_t* n_contrib;
-    uint32_t R; int P;                       // what the lists were laid out for: fences for a stale img
+struct ContribArgs : ReplayArgs {
     const float* pixel_weight;               // opt [H*W]
     const int32_t* row_map;                  // opt [P]: the record Gaussian g is accumulated into
     uint32_t* rows;                          // [P] records of four words: weight_sum (f32), weight_max (f32), pixels, tiles
@@ -634,73 +555,47 @@ struct ContribArgs : BlendHead {
 
 __global__ void __launch_bounds__(256) render_contrib_kernel(ContribArgs a) {
 #pragma clang fp contract(off)
-    const int tile = unit_lookup(a.order, a.per_xcd, blockIdx.x, a.gx, a.gy, 1, a.bh);
-    if (tile < 0 || tile >= a.gx * a.gy) return;
+    const ReplayPixel px = replay_pixel<false>(a);
+    if (px.tile < 0) return;
     __shared__ float4 sA[256], sB[256];
     __shared__ uint32_t sG[256];
     __shared__ uint4 sAcc[256 * 4];          // [entry][wave]: the bits of the sum, the bits of the maximum, the count, unused
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int x = (tile % a.gx) * TILE + (t & 15), y = (tile / a.gx) * TILE + (t >> 4);
-    const bool inside = x < a.W && y < a.H;
-    const float pxf = (float)x, pyf = (float)y;
-    const size_t pix = (size_t)y * a.W + x;
-    uint2 range = a.ranges[tile];
-    range.y = range.y < a.R ? range.y : a.R;
-    range.x = range.x < range.y ? range.x : range.y;
-    const uint32_t walk = a.tile_todo[tile];
-    uint32_t own = inside ? a.n_contrib[pix] : 0u;
+    uint32_t own = px.own;
     float m = 1.0f;
     if (a.pixel_weight) {
-        m = inside ? a.pixel_weight[pix] : 0.0f;
+        m = px.inside ? a.pixel_weight[px.pix] : 0.0f;
         if (!(m > 0.0f)) own = 0u;           // zero, negative, NaN: no v of this pixel is > 0
     }
-    const int n_list = (int)(range.y - range.x);
-    const int todo = walk < (uint32_t)n_list ? (int)walk : n_list;           // the tile's walk length, clamped to the list ...
-    const int mine = own < (uint32_t)todo ? (int)own : todo;                // ... and this lane's, clamped to the tile's
-    const int rounds = (todo + 255) / 256;
-    int wave_mine = mine;                                                    // the longest walk among the wave's 64 pixels
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int u = __shfl_xor(wave_mine, o, 64); wave_mine = u > wave_mine ? u : wave_mine; }
+    const ReplayLengths len = replay_lengths<false>(a, px.tile, own);
+    const int wave_mine = replay_wave_mine(len.mine);
     float T = 1.0f;
     int seen = 0;                            // entries of the list this lane has passed
-    auto gid_of = [&](int r) -> uint32_t {
-        const int e = r * 256 + t;
-        return a.pair_gid[range.x + (e < n_list ? e : n_list - 1)];
-    };
     uint32_t g_cur = 0u, g_nxt = 0u;
     float4 rA, rB;
-    if (rounds > 0) {
-        g_cur = gid_of(0);
-        if (rounds > 1) g_nxt = gid_of(1);
+    if (len.rounds > 0) {
+        g_cur = replay_gid(a, len, 0);
+        if (len.rounds > 1) g_nxt = replay_gid(a, len, 1);
         rA = a.recA[g_cur]; rB = a.recB[g_cur];
     }
-    for (int r = 0; r < rounds; r++) {
-        if (__syncthreads_count(seen >= mine) == 256) break;
-        const int left = todo - r * 256;
+    for (int r = 0; r < len.rounds; r++) {
+        if (__syncthreads_count(seen >= len.mine) == 256) break;
+        const int left = len.todo - r * 256;
         const int staged = left < 256 ? left : 256;                         // entries of this round
         sA[t] = rA; sB[t] = rB; sG[t] = g_cur;
         for (int k = t; k < staged * 4; k += 256) sAcc[k] = make_uint4(0u, 0u, 0u, 0u);      // (an entry a wave does not hit keeps a zero slot)
         __syncthreads();
-        if (r + 1 < rounds) { g_cur = g_nxt; rA = a.recA[g_cur]; rB = a.recB[g_cur]; }
-        if (r + 2 < rounds) g_nxt = gid_of(r + 2);
-        const int rem = mine - seen;
+        if (r + 1 < len.rounds) { g_cur = g_nxt; rA = a.recA[g_cur]; rB = a.recB[g_cur]; }
+        if (r + 2 < len.rounds) g_nxt = replay_gid(a, len, r + 2);
+        const int rem = len.mine - seen;
         const int wave_rem = wave_mine - seen;
         const int lim = wave_rem < staged ? wave_rem : staged;
         for (int j = 0; j < lim; j++) {
             float v = 0.0f;
             if (j < rem) {
-                const float4 Aj = sA[j];
-                const float4 B = sB[j];
-                const float dx = Aj.x - pxf, dy = Aj.y - pyf;
-                const float power = blend_power(blend_power_xx(Aj.z, dx), blend_power_xy(Aj.w, dx), B.x, dy);
-                if (!(power > 0.0f)) {
-                    const float alpha = fminf(FDGS_ALPHA_MAX, B.y * __expf(power));
-                    if (!(alpha < FDGS_ALPHA_MIN)) {
-                        const float w = alpha * T;
-                        v = w * m;
-                        T = T * (1.0f - alpha);
-                    }
-                }
+                const ReplayWeight e = replay_weight(sA[j], sB[j], px.pxf, px.pyf, T);
+                v = e.w * m;                 // (skipped: +0 * m -- +0, or a NaN for an infinite m -- and not > 0 either way)
+                T = e.T;
             }
             const bool hit = v > 0.0f;
             const unsigned long long hits = __ballot(hit);
@@ -713,10 +608,8 @@ __global__ void __launch_bounds__(256) render_contrib_kernel(ContribArgs a) {
         seen += 256;
         __syncthreads();
         auto record_of = [&](int jj) -> uint32_t* {                          // where entry jj is accumulated, nullptr: dropped
-            const uint32_t g = sG[jj];
-            if (g >= (uint32_t)a.P) return nullptr;
-            const uint32_t row = a.row_map ? (uint32_t)a.row_map[g] : g;
-            return row < (uint32_t)a.P ? a.rows + (size_t)row * 4 : nullptr;
+            const int32_t row = replay_row(a, sG[jj], a.row_map, (uint32_t)a.P);
+            return row >= 0 ? a.rows + (size_t)row * 4 : nullptr;
         };
 #if FDGS_CONTRIB_FLUSH_LANES == 4
         const int sub = t & 3;
@@ -1114,8 +1007,8 @@ int launch_tile_scan_order(hipStream_t stream, const ImgLayout& il, const uint32
     return FDGS_OK;
 }
 
-// what both blending launchers set from the frame's buffers (Args = RenderArgs with a writable img, RenderBwdArgs with a const one);
-// `order` stays with the launcher: making it is a launch
+// what both blending launchers set from the frame's buffers (Args = RenderArgs with a writable img, RenderBwdArgs with a const one; the
+// replay passes have fill_replay_args); `order` stays with the launcher: making it is a launch
 template <typename Args, typename Img>
 static ImgLayout fill_blend_args(Args& a, const fdgs_raster_params* p, const void* geom, const void* binning, Img* img, uint32_t R) {
     const GeomLayout gl = geom_layout(p->P);
@@ -1126,6 +1019,31 @@ static ImgLayout fill_blend_args(Args& a, const fdgs_raster_params* p, const voi
     a.recA = at<float4>(geom, gl.recA); a.recB = at<float4>(geom, gl.recB); a.recC = at<float4>(geom, gl.recC);
     a.bg = p->bg; a.final_T = at<float>(img, il.final_T); a.n_contrib = at<uint32_t>(img, il.n_contrib);
     return il;
+}
+
+// what the four replay entry points (fdgs_render_pick / _features / _features_bwd / _contrib) check first; `pointers`: the call's own
+// required pointers, p among them, are all there
+static int check_replay_call(bool pointers, const char* null_msg, const fdgs_raster_params* p) {
+    FDGS_REQUIRE(pointers, null_msg);
+    FDGS_REQUIRE(p->P >= 0 && p->W >= 1 && p->H >= 1, "bad P/W/H");
+    FDGS_REQUIRE((p->W + TILE - 1) / TILE < 65536 && (p->H + TILE - 1) / TILE < 65536, "image too large");
+    return FDGS_OK;
+}
+
+// every field of a replay kernel's ReplayArgs from the finished frame's buffers.  `order` is the forward's own heaviest-first order where
+// fdgs_render_fwd wrote one (make_tile_order's condition), never rebuilt here.  Of *p only P, W and H are read and none of its pointers is
+// looked at: a later frame may have overwritten what they named.
+static void fill_replay_args(ReplayArgs& a, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img, uint32_t R) {
+    const GeomLayout gl = geom_layout(p->P);
+    const BinLayout bl = bin_layout(R);
+    const ImgLayout il = img_layout(p->W, p->H);
+    a.W = p->W; a.H = p->H; a.gx = il.gx; a.gy = il.gy; a.bh = XCD_ROWS; a.per_xcd = il.per_xcd;
+    a.empty = (p->P == 0 || R == 0) ? 1 : 0;
+    a.order = !a.empty && tiles_ordered(il) ? at<uint32_t>(img, il.order_f) : nullptr;
+    a.tile_todo = at<uint32_t>(img, il.todo); a.ranges = at<uint2>(img, il.ranges); a.pair_gid = at<uint32_t>(binning, bl.gid0);
+    a.recA = at<float4>(geom, gl.recA); a.recB = at<float4>(geom, gl.recB);
+    a.n_contrib = at<uint32_t>(img, il.n_contrib);
+    a.R = R; a.P = p->P;
 }
 
 // The blending backward's form.  ppl = pixels per lane of the strip form (one wave per workgroup, 4 / ppl of them per tile); anything but
@@ -1173,24 +1091,16 @@ extern "C" int fdgs_render_fwd(void* stream_, const fdgs_raster_params* p, const
 
 extern "C" int fdgs_render_pick(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
                                 uint32_t R, float alpha_cut, const int32_t* row_map_opt, const fdgs_pick_out* out) {
-    FDGS_REQUIRE(p && geom && binning && img && out, "NULL pointer (params, geom, binning, img and out)");
-    FDGS_REQUIRE(p->P >= 0 && p->W >= 1 && p->H >= 1, "bad P/W/H");
-    FDGS_REQUIRE((p->W + TILE - 1) / TILE < 65536 && (p->H + TILE - 1) / TILE < 65536, "image too large");
+    if (int rc = check_replay_call(p && geom && binning && img && out, "NULL pointer (params, geom, binning, img and out)", p)) return rc;
     FDGS_REQUIRE(alpha_cut > 0.0f && alpha_cut <= 1.0f, "bad alpha_cut (in (0, 1]; a NaN is refused)");
     FDGS_REQUIRE(out->pick_id || out->pick_weight || out->surface_id || out->surface_depth, "NULL pointer (at least one output)");
     FDGS_REQUIRE(aligned_to(out->pick_id, 4) && aligned_to(out->pick_weight, 4) && aligned_to(out->surface_id, 4) &&
                      aligned_to(out->surface_depth, 4) && aligned_to(row_map_opt, 4), "arrays must be 4-byte aligned");
     hipStream_t stream = (hipStream_t)stream_;
     PickArgs a{};
-    const ImgLayout il = fill_blend_args(a, p, geom, binning, img, R);
-    a.tile_todo = at<uint32_t>(img, il.todo);
-    a.R = R; a.P = p->P;
-    a.empty = (p->P == 0 || R == 0) ? 1 : 0;
+    fill_replay_args(a, p, geom, binning, img, R);
     a.alpha_cut = alpha_cut; a.row_map = row_map_opt;
     a.pick_id = out->pick_id; a.pick_weight = out->pick_weight; a.surface_id = out->surface_id; a.surface_depth = out->surface_depth;
-    // the forward's own heaviest-first order, where fdgs_render_fwd wrote one (make_tile_order's condition); never rebuilt here
-    const bool ordered = !a.empty && tiles_ordered(il);
-    a.order = ordered ? at<uint32_t>(img, il.order_f) : nullptr;
     {
         FDGS_TIMED("render_pick", stream);
         hipLaunchKernelGGL(render_pick_kernel, dim3(unit_grid(a.gx, a.gy, 1, a.bh)), dim3(256), 0, stream, a);
@@ -1202,9 +1112,8 @@ extern "C" int fdgs_render_pick(void* stream_, const fdgs_raster_params* p, cons
 extern "C" int fdgs_render_features(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
                                     uint32_t R, int C, const float* values, int value_stride, int rows, const int32_t* row_map_opt,
                                     float min_alpha, float* features, float* alpha_opt) {
-    FDGS_REQUIRE(p && geom && binning && img && values && features, "NULL pointer (params, geom, binning, img, values and features)");
-    FDGS_REQUIRE(p->P >= 0 && p->W >= 1 && p->H >= 1, "bad P/W/H");
-    FDGS_REQUIRE((p->W + TILE - 1) / TILE < 65536 && (p->H + TILE - 1) / TILE < 65536, "image too large");
+    if (int rc = check_replay_call(p && geom && binning && img && values && features, "NULL pointer (params, geom, binning, img, values and features)", p))
+        return rc;
     FDGS_REQUIRE(C >= 1 && C <= 8 * 65535, "bad C (1 .. 8 * 65535 channels)");
     FDGS_REQUIRE(value_stride >= C, "bad value_stride (at least C floats per row)");
     FDGS_REQUIRE(rows >= 0, "bad rows (negative)");
@@ -1212,16 +1121,10 @@ extern "C" int fdgs_render_features(void* stream_, const fdgs_raster_params* p, 
                  "arrays must be 4-byte aligned");
     hipStream_t stream = (hipStream_t)stream_;
     FeatArgs a{};
-    const ImgLayout il = fill_blend_args(a, p, geom, binning, img, R);
-    a.tile_todo = at<uint32_t>(img, il.todo);
-    a.R = R; a.P = p->P;
-    a.empty = (p->P == 0 || R == 0) ? 1 : 0;
+    fill_replay_args(a, p, geom, binning, img, R);
     a.C = C; a.values = values; a.value_stride = value_stride; a.rows = rows; a.row_map = row_map_opt;
     a.min_alpha = min_alpha >= 0.0f ? min_alpha : -1.0f;                    // (negative or NaN: raw sums)
     a.features = features; a.alpha = alpha_opt;
-    // the forward's own heaviest-first order, where fdgs_render_fwd wrote one (make_tile_order's condition); never rebuilt here
-    const bool ordered = !a.empty && tiles_ordered(il);
-    a.order = ordered ? at<uint32_t>(img, il.order_f) : nullptr;
     {
         FDGS_TIMED("render_features", stream);
         hipLaunchKernelGGL(render_features_kernel, dim3(unit_grid(a.gx, a.gy, 1, a.bh), (C + FEAT_CH - 1) / FEAT_CH), dim3(256), 0, stream, a);
@@ -1233,9 +1136,9 @@ extern "C" int fdgs_render_features(void* stream_, const fdgs_raster_params* p, 
 extern "C" int fdgs_render_features_bwd(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
                                         uint32_t R, int C, const float* dL_dfeatures, const float* alpha_opt, float min_alpha,
                                         const int32_t* row_map_opt, int rows, float* dvalues, int dvalue_stride) {
-    FDGS_REQUIRE(p && geom && binning && img && dL_dfeatures && dvalues, "NULL pointer (params, geom, binning, img, dL_dfeatures and dvalues)");
-    FDGS_REQUIRE(p->P >= 0 && p->W >= 1 && p->H >= 1, "bad P/W/H");
-    FDGS_REQUIRE((p->W + TILE - 1) / TILE < 65536 && (p->H + TILE - 1) / TILE < 65536, "image too large");
+    if (int rc = check_replay_call(p && geom && binning && img && dL_dfeatures && dvalues,
+                                   "NULL pointer (params, geom, binning, img, dL_dfeatures and dvalues)", p))
+        return rc;
     FDGS_REQUIRE(C >= 1 && C <= 8 * 65535, "bad C (1 .. 8 * 65535 channels)");
     FDGS_REQUIRE(dvalue_stride >= C, "bad dvalue_stride (at least C floats per row)");
     FDGS_REQUIRE(rows >= 0, "bad rows (negative)");
@@ -1246,19 +1149,10 @@ extern "C" int fdgs_render_features_bwd(void* stream_, const fdgs_raster_params*
     if (p->P == 0 || R == 0) return FDGS_OK;          // nothing was blended: nothing is accumulated, nothing is launched
     hipStream_t stream = (hipStream_t)stream_;
     // (of *p only P, W, H and debug are read and none of its pointers is looked at: a later frame may have overwritten what they named)
-    const GeomLayout gl = geom_layout(p->P);
-    const BinLayout bl = bin_layout(R);
-    const ImgLayout il = img_layout(p->W, p->H);
     FeatBwdArgs a{};
-    a.W = p->W; a.H = p->H; a.gx = il.gx; a.gy = il.gy; a.bh = XCD_ROWS; a.per_xcd = il.per_xcd;
-    a.ranges = at<uint2>(img, il.ranges); a.pair_gid = at<uint32_t>(binning, bl.gid0);
-    a.recA = at<float4>(geom, gl.recA); a.recB = at<float4>(geom, gl.recB);
-    a.n_contrib = at<uint32_t>(img, il.n_contrib); a.tile_todo = at<uint32_t>(img, il.todo);
-    a.R = R; a.P = p->P;
+    fill_replay_args(a, p, geom, binning, img, R);
     a.C = C; a.grad = dL_dfeatures; a.alpha = normalized ? alpha_opt : nullptr; a.min_alpha = normalized ? min_alpha : -1.0f;
     a.row_map = row_map_opt; a.rows = rows; a.dvalues = dvalues; a.dvalue_stride = dvalue_stride;
-    // the forward's own heaviest-first order, where fdgs_render_fwd wrote one (make_tile_order's condition); never rebuilt here
-    a.order = tiles_ordered(il) ? at<uint32_t>(img, il.order_f) : nullptr;
     {
         FDGS_TIMED("render_features_bwd", stream);
         hipLaunchKernelGGL(render_features_bwd_kernel, dim3(unit_grid(a.gx, a.gy, 1, a.bh), (C + FEAT_CH - 1) / FEAT_CH), dim3(256), 0, stream, a);
@@ -1269,21 +1163,15 @@ extern "C" int fdgs_render_features_bwd(void* stream_, const fdgs_raster_params*
 
 extern "C" int fdgs_render_contrib(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
                                    uint32_t R, const float* pixel_weight_opt, const int32_t* row_map_opt, fdgs_contrib_row* rows) {
-    FDGS_REQUIRE(p && geom && binning && img && rows, "NULL pointer (params, geom, binning, img and rows)");
-    FDGS_REQUIRE(p->P >= 0 && p->W >= 1 && p->H >= 1, "bad P/W/H");
-    FDGS_REQUIRE((p->W + TILE - 1) / TILE < 65536 && (p->H + TILE - 1) / TILE < 65536, "image too large");
+    if (int rc = check_replay_call(p && geom && binning && img && rows, "NULL pointer (params, geom, binning, img and rows)", p)) return rc;
     FDGS_REQUIRE(aligned_to(rows, 16), "rows must be 16-byte aligned");
     FDGS_REQUIRE(aligned_to(pixel_weight_opt, 4) && aligned_to(row_map_opt, 4), "pixel_weight_opt and row_map_opt must be 4-byte aligned");
     if (p->P == 0 || R == 0) return FDGS_OK;          // nothing was blended: nothing is accumulated, nothing is launched
     hipStream_t stream = (hipStream_t)stream_;
     ContribArgs a{};
-    const ImgLayout il = fill_blend_args(a, p, geom, binning, img, R);
-    a.tile_todo = at<uint32_t>(img, il.todo);
-    a.R = R; a.P = p->P;
+    fill_replay_args(a, p, geom, binning, img, R);
     a.pixel_weight = pixel_weight_opt; a.row_map = row_map_opt;
     a.rows = reinterpret_cast<uint32_t*>(rows);
-    // the forward's own heaviest-first order, where fdgs_render_fwd wrote one (make_tile_order's condition); never rebuilt here
-    a.order = tiles_ordered(il) ? at<uint32_t>(img, il.order_f) : nullptr;
     {
         FDGS_TIMED("render_contrib", stream);
         hipLaunchKernelGGL(render_contrib_kernel, dim3(unit_grid(a.gx, a.gy, 1, a.bh)), dim3(256), 0, stream, a);

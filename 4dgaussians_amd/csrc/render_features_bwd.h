@@ -1,13 +1,11 @@
 // render_features_bwd.h -- the adjoint of the feature pass with respect to its values (included by render.hip, inside namespace fdgs,
-// behind render_features_kernel: it uses that unit's BlendHead, unit_lookup, blend_power* and FEAT_CH).
+// behind render_features_kernel: it uses that unit's replay walk, blend_replay.h, and FEAT_CH).
 //
 //     dvalues[row, c] += sum over the frame's pixels of w(row, pixel) * G[c, pixel],      G = dL/dfeatures
 //
-// The walk is render_features_kernel's: one 256-thread workgroup per tile and chunk of FEAT_CH = 16 channels (blockIdx.y), tiles taken in
-// the order the forward left in img, recA / recB / the ids staged in rounds of 256 one round (the ids: two) ahead, every walk clamped to
-// the tile's range, tile_todo, num_rendered and the lane's n_contrib, compiled without contraction with the forward's expressions: w =
-// alpha * T has the bits the forward blended with.  What differs is where w goes.  Per tile and chunk the work is a small GEMM,
-// dV[entry, c] = sum over the 256 pixels of w[entry, pixel] * G[c, pixel], and the contraction over the pixels runs on the matrix cores:
+// A replay walk that stages the ids, one workgroup per tile and chunk of FEAT_CH = 16 channels (blockIdx.y) as render_features_kernel's.
+// What differs is where w goes.  Per tile and chunk the work is a small GEMM, dV[entry, c] = sum over the 256 pixels of
+// w[entry, pixel] * G[c, pixel], and the contraction over the pixels runs on the matrix cores:
 //
 //   * a wave owns 64 pixels (four lines of the tile).  Its operand G -- 64 pixels x 16 channels -- is loaded ONCE per tile and chunk, one
 //     coalesced load per channel with the lane's own pixel, scaled on the way for a normalised forward (G / A, IEEE division, where
@@ -39,12 +37,7 @@ static_assert(FEAT_CH == 16, "render_features_bwd_kernel: one 16x16x4 MFMA tile 
 
 typedef float fbwd_f32x4 __attribute__((ext_vector_type(4)));
 
-struct FeatBwdArgs : BlendHead {
-    const uint32_t* tile_todo;               // per tile: max n_contrib, the forward's walk length
-    const uint2* ranges; const uint32_t* pair_gid;
-    const float4 *recA, *recB;
-    const uint32_t* n_contrib;
-    uint32_t R; int P;                       // what the lists were laid out for: fences for a stale img
+struct FeatBwdArgs : ReplayArgs {
     int C; const float* grad;                // dL/dfeatures [C,H,W]
     const float* alpha; float min_alpha;     // min_alpha >= 0: the forward divided by A = alpha[pixel] where A > min_alpha
     const int32_t* row_map; int rows;        // opt [P]: the row of `dvalues` Gaussian g is accumulated into
@@ -68,8 +61,8 @@ __device__ __forceinline__ void park_transpose(float* park, int lane, float (&v)
 
 __global__ void __launch_bounds__(256) render_features_bwd_kernel(FeatBwdArgs a) {
 #pragma clang fp contract(off)
-    const int tile = unit_lookup(a.order, a.per_xcd, blockIdx.x, a.gx, a.gy, 1, a.bh);
-    if (tile < 0 || tile >= a.gx * a.gy) return;
+    const ReplayPixel px = replay_pixel<false>(a);
+    if (px.tile < 0) return;
     __shared__ float4 sA[256], sB[256];
     __shared__ uint32_t sG[256];
     __shared__ float sPark[4][16 * FBWD_PARK];
@@ -78,28 +71,12 @@ __global__ void __launch_bounds__(256) render_features_bwd_kernel(FeatBwdArgs a)
     float* const park = sPark[wv];
     const int c0 = (int)blockIdx.y * FEAT_CH;                                // this chunk's first channel
     const int nch = a.C - c0 < FEAT_CH ? a.C - c0 : FEAT_CH;                 // ... and how many of its sixteen exist (>= 1: the grid)
-    const int x = (tile % a.gx) * TILE + (t & 15), y = (tile / a.gx) * TILE + (t >> 4);
-    const bool inside = x < a.W && y < a.H;
-    const float pxf = (float)x, pyf = (float)y;
-    const size_t pix = (size_t)y * a.W + x, hw = (size_t)a.H * a.W;
-    uint2 range = a.ranges[tile];
-    range.y = range.y < a.R ? range.y : a.R;
-    range.x = range.x < range.y ? range.x : range.y;
-    const uint32_t walk = a.tile_todo[tile];
-    const uint32_t own = inside ? a.n_contrib[pix] : 0u;
-    const int n_list = (int)(range.y - range.x);
-    const int todo = walk < (uint32_t)n_list ? (int)walk : n_list;           // the tile's walk length, clamped to the list ...
-    const int mine = own < (uint32_t)todo ? (int)own : todo;                // ... and this lane's, clamped to the tile's
-    const int rounds = (todo + 255) / 256;
-    if (rounds == 0) return;                                                 // (uniform: nothing was blended into this tile)
-    int wave_mine = mine;                                                    // the longest walk among the wave's 64 pixels
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int u = __shfl_xor(wave_mine, o, 64); wave_mine = u > wave_mine ? u : wave_mine; }
-    auto gid_of = [&](int r) -> uint32_t {
-        const int e = r * 256 + t;
-        return a.pair_gid[range.x + (e < n_list ? e : n_list - 1)];
-    };
-    uint32_t g_cur = gid_of(0), g_nxt = rounds > 1 ? gid_of(1) : 0u;
+    const bool inside = px.inside;
+    const size_t pix = px.pix, hw = (size_t)a.H * a.W;
+    const ReplayLengths len = replay_lengths<false>(a, px.tile, px.own);
+    if (len.rounds == 0) return;                                             // (uniform: nothing was blended into this tile)
+    const int wave_mine = replay_wave_mine(len.mine);
+    uint32_t g_cur = replay_gid(a, len, 0), g_nxt = len.rounds > 1 ? replay_gid(a, len, 1) : 0u;
     float4 rA = a.recA[g_cur], rB = a.recB[g_cur];
     // the wave's operand G: channel k of the lane's own pixel, then transposed once
     float gop[16];
@@ -123,15 +100,15 @@ __global__ void __launch_bounds__(256) render_features_bwd_kernel(FeatBwdArgs a)
     }
     float T = 1.0f;
     int seen = 0;                            // entries of the list this lane has passed
-    for (int r = 0; r < rounds; r++) {
-        if (__syncthreads_count(seen >= mine) == 256) break;
-        const int left = todo - r * 256;
+    for (int r = 0; r < len.rounds; r++) {
+        if (__syncthreads_count(seen >= len.mine) == 256) break;
+        const int left = len.todo - r * 256;
         const int staged = left < 256 ? left : 256;                         // entries of this round
         sA[t] = rA; sB[t] = rB; sG[t] = g_cur;
         __syncthreads();
-        if (r + 1 < rounds) { g_cur = g_nxt; rA = a.recA[g_cur]; rB = a.recB[g_cur]; }
-        if (r + 2 < rounds) g_nxt = gid_of(r + 2);
-        const int rem = mine - seen;
+        if (r + 1 < len.rounds) { g_cur = g_nxt; rA = a.recA[g_cur]; rB = a.recB[g_cur]; }
+        if (r + 2 < len.rounds) g_nxt = replay_gid(a, len, r + 2);
+        const int rem = len.mine - seen;
         const int wave_rem = wave_mine - seen;
         const int lim = wave_rem < staged ? wave_rem : staged;              // where this wave's walk of the round ends
         for (int j0 = 0; j0 < staged; j0 += 16) {                           // (uniform over the workgroup)
@@ -144,17 +121,9 @@ __global__ void __launch_bounds__(256) render_features_bwd_kernel(FeatBwdArgs a)
                     const int j = j0 + k;                                    // (< 256: sA / sB hold a record for every j, a copy of the list's last behind its end)
                     float w = 0.0f;
                     if (j < rem) {
-                        const float4 Aj = sA[j];
-                        const float4 B = sB[j];
-                        const float dx = Aj.x - pxf, dy = Aj.y - pyf;
-                        const float power = blend_power(blend_power_xx(Aj.z, dx), blend_power_xy(Aj.w, dx), B.x, dy);
-                        if (!(power > 0.0f)) {
-                            const float alpha = fminf(FDGS_ALPHA_MAX, B.y * __expf(power));
-                            if (!(alpha < FDGS_ALPHA_MIN)) {
-                                w = alpha * T;
-                                T = T * (1.0f - alpha);
-                            }
-                        }
+                        const ReplayWeight e = replay_weight(sA[j], sB[j], px.pxf, px.pyf, T);
+                        w = e.w;
+                        T = e.T;
                     }
                     w16[k] = w;
                     any = any || w > 0.0f;
@@ -188,12 +157,8 @@ __global__ void __launch_bounds__(256) render_features_bwd_kernel(FeatBwdArgs a)
                 if (h2) s = s + sPark[2][t];
                 if (h3) s = s + sPark[3][t];
                 if (jj < staged && ch < nch && s != 0.0f) {
-                    const uint32_t g = sG[jj];
-                    if (g < (uint32_t)a.P) {
-                        const uint32_t row = a.row_map ? (uint32_t)a.row_map[g] : g;
-                        if (row < (uint32_t)a.rows)                          // (a -1 of the map is >= rows as well)
-                            atomicAdd(a.dvalues + (size_t)row * (size_t)a.dvalue_stride + (size_t)(c0 + ch), s);
-                    }
+                    const int32_t row = replay_row(a, sG[jj], a.row_map, (uint32_t)a.rows);
+                    if (row >= 0) atomicAdd(a.dvalues + (size_t)row * (size_t)a.dvalue_stride + (size_t)(c0 + ch), s);
                 }
             }
             __syncthreads();                                                 // (the next block's transpose rewrites the parks, its end sHit)
