@@ -136,6 +136,11 @@ SYMBOLS = {
     "fdgs_raster_fwd_capacity": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdgs_pair_count_wait": (c_int, [c_void_p, c_void_p, POINTER(c_uint32)]),
     "fdgs_raster_bwd": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_uint32, POINTER(RasterGrads)]),
+    # ... with the accumulated opacity: one more image out, its gradient in (NULL: the call above)
+    "fdgs_render_fwd_alpha": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "fdgs_raster_fwd_capacity_alpha": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p]),
+    "fdgs_raster_bwd_alpha": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_uint32, POINTER(RasterGrads), c_void_p]),
     "fdgs_mark_visible": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdgs_preprocess_host": (c_int, [POINTER(RasterParams)] + [c_void_p] * 9),
     "fdgs_preprocess_bwd_host": (c_int, [POINTER(RasterParams)] + [c_void_p] * 13),

@@ -819,8 +819,9 @@ extern "C" int fdgs_bin_sort(void* stream_, const fdgs_raster_params* p, void* g
     return bin_sort_impl(stream_, p, geom, binning, img, R, false);
 }
 
-extern "C" int fdgs_raster_fwd_capacity(void* stream, const fdgs_raster_params* p, void* geom, void* binning, void* img, uint32_t capacity,
-                                        uint32_t* num_rendered_host, int32_t* radii, float* out_color, float* out_depth) {
+// fdgs_raster_fwd_capacity (out_alpha == nullptr) and fdgs_raster_fwd_capacity_alpha
+static int raster_fwd_capacity_impl(void* stream, const fdgs_raster_params* p, void* geom, void* binning, void* img, uint32_t capacity,
+                                    uint32_t* num_rendered_host, int32_t* radii, float* out_color, float* out_depth, float* out_alpha) {
     FDGS_REQUIRE(capacity > 0 && binning, "capacity mode needs a binning buffer of fdgs_binning_bytes(capacity) bytes, capacity > 0");
     // the count's way to the host: a store by the LAST workgroup of the projection kernel into the (pinned, device-visible) word -- it is in
     // host memory while the depth sort is still running; a copy node if the word is not device-visible (a 4-byte copy costs the stream
@@ -836,7 +837,17 @@ extern "C" int fdgs_raster_fwd_capacity(void* stream, const fdgs_raster_params* 
     bool order_made = false;
     rc = bin_sort_impl(stream, p, geom, binning, img, capacity, true, nullptr, counted, &order_made);
     if (rc) return rc;
-    return render_fwd_impl(stream, p, geom, binning, img, capacity, out_color, out_depth, order_made);
+    return render_fwd_impl(stream, p, geom, binning, img, capacity, out_color, out_depth, order_made, out_alpha);
+}
+
+extern "C" int fdgs_raster_fwd_capacity(void* stream, const fdgs_raster_params* p, void* geom, void* binning, void* img, uint32_t capacity,
+                                        uint32_t* num_rendered_host, int32_t* radii, float* out_color, float* out_depth) {
+    return raster_fwd_capacity_impl(stream, p, geom, binning, img, capacity, num_rendered_host, radii, out_color, out_depth, nullptr);
+}
+
+extern "C" int fdgs_raster_fwd_capacity_alpha(void* stream, const fdgs_raster_params* p, void* geom, void* binning, void* img, uint32_t capacity,
+                                              uint32_t* num_rendered_host, int32_t* radii, float* out_color, float* out_depth, float* out_alpha) {
+    return raster_fwd_capacity_impl(stream, p, geom, binning, img, capacity, num_rendered_host, radii, out_color, out_depth, out_alpha);
 }
 
 // Host side of the verified capacity path: wait until the pair count of a frame queued by fdgs_raster_fwd_capacity has reached its pinned

@@ -19,9 +19,10 @@ bool counts_in_projection(const ImgLayout& il);
 // the blending takes its tiles heaviest-first, the forward's tile order from the same counts.  *order_made: the order stands in img.
 int launch_tile_scan_order(hipStream_t stream, const ImgLayout& il, const uint32_t* counts, void* img, uint32_t cap, int debug, bool* order_made);
 
-// fdgs_render_fwd; order_made: the forward's tile order already stands in img (launch_tile_scan_order), no launch makes it
+// fdgs_render_fwd / fdgs_render_fwd_alpha; order_made: the forward's tile order already stands in img (launch_tile_scan_order), no launch
+// makes it; out_alpha: opt [H*W], the accumulated opacity
 int render_fwd_impl(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, void* img, uint32_t R, float* out_color,
-                    float* out_depth, bool order_made);
+                    float* out_depth, bool order_made, float* out_alpha);
 
 }  // namespace fdgs
 

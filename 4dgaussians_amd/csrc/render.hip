@@ -179,6 +179,7 @@ struct RenderArgs : BlendHead {
     const float* bg;
     float* final_T; uint32_t* n_contrib;
     float *out_color, *out_depth;
+    float* out_alpha;                        // opt [H*W]: the accumulated opacity 1 - final_T (fdgs_render_fwd_alpha)
     float4* zfill; uint32_t zfill_n4;        // opt: a range zero-filled on the way (fdgs_raster_params::acc_zero: the backward's accumulator)
 };
 
@@ -302,6 +303,7 @@ __global__ void __launch_bounds__(256) render_fwd_kernel(RenderArgs a) {
         a.out_color[hw + pix] = C1 + T * a.bg[1];
         a.out_color[2 * hw + pix] = C2 + T * a.bg[2];
         a.out_depth[pix] = Dp;
+        if (a.out_alpha) a.out_alpha[pix] = 1.0f - T;        // (the T stored to final_T above: an empty list gives exactly 0)
     }
     {   // the tile's walk length for the backward (its work: the key of the backward's heaviest-first order)
         uint32_t m = inside ? last : 0u;
@@ -678,6 +680,7 @@ struct RenderBwdArgs : BlendHead {
     const float* bg;
     const float* final_T; const uint32_t* n_contrib;
     const float *dL_dcolor, *dL_ddepth;
+    const float* dL_dalpha;                  // opt [H*W]: gradient of the accumulated opacity A = 1 - final_T (fdgs_raster_bwd_alpha)
     float* gacc;  // [P,16] per-Gaussian gradient line: 0,1 mean2D (pixel units) | 2,3,4 conic xx,xy(half),yy | 5 opacity |
                   // 6,7,8 rgb | 9 depth | 10..15 unused.  One 64-B line per Gaussian => one atomic line-op per (tile,Gaussian)
 };
@@ -725,7 +728,9 @@ __global__ void __launch_bounds__(256) render_bwd_kernel(RenderBwdArgs a) {
         dp0 = a.dL_dcolor[pix]; dp1 = a.dL_dcolor[hw + pix]; dp2 = a.dL_dcolor[2 * hw + pix];
         if (DEPTH) ddep = a.dL_ddepth[pix];
     }
-    const float bgdot = a.bg[0] * dp0 + a.bg[1] * dp1 + a.bg[2] * dp2;
+    // dA/dalpha_i = T_final / (1 - alpha_i) is the background term's factor with the sign turned: a gradient of the accumulated opacity
+    // enters here, once per pixel, and the list walk below is the one a frame without it runs (x - 0 is x: the same bits when NULL)
+    const float bgdot = (a.bg[0] * dp0 + a.bg[1] * dp1 + a.bg[2] * dp2) - ((inside && a.dL_dalpha) ? a.dL_dalpha[pix] : 0.f);
     float T = T_final, acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, accd = 0.f;
     float lc0 = 0.f, lc1 = 0.f, lc2 = 0.f, ld = 0.f, last_alpha = 0.f;
     const int rounds = (toDo + ROUND - 1) / ROUND;
@@ -863,6 +868,7 @@ __global__ void __launch_bounds__(64) render_bwd_strip_kernel(RenderBwdArgs a) {
     const bool slot_on = (lane & 15) < 4 && (lane < 32 || (lane < 48 && (lane & 15) < (DEPTH ? 2 : 1)));
     const uint2 range = a.ranges[tile];
     v2f py[NP], T[NP], tfb[NP], dp0[NP], dp1[NP], dp2[NP], ddep[NP], acc0[NP], acc1[NP], acc2[NP], accd[NP];
+    v2f dal[NP];                         // dL/dA of the pixels (0 without a.dL_dalpha): only lives until tfb is formed
     uint32_t lastc[PPL];
     uint32_t m = 0;
 #pragma unroll
@@ -878,11 +884,13 @@ __global__ void __launch_bounds__(64) render_bwd_strip_kernel(RenderBwdArgs a) {
         dp1[p][c] = inside ? a.dL_dcolor[hw + pix] : 0.f;
         dp2[p][c] = inside ? a.dL_dcolor[2 * hw + pix] : 0.f;
         ddep[p][c] = (DEPTH && inside) ? a.dL_ddepth[pix] : 0.f;
+        dal[p][c] = (inside && a.dL_dalpha) ? a.dL_dalpha[pix] : 0.f;
         m = lastc[i] > m ? lastc[i] : m;
     }
 #pragma unroll
     for (int p = 0; p < NP; p++) {
-        tfb[p] = -T[p] * (a.bg[0] * dp0[p] + a.bg[1] * dp1[p] + a.bg[2] * dp2[p]);
+        // (dA/dalpha_i = T_final / (1 - alpha_i), the background term's factor with the sign turned: x - 0 is x, the same bits without it)
+        tfb[p] = -T[p] * ((a.bg[0] * dp0[p] + a.bg[1] * dp1[p] + a.bg[2] * dp2[p]) - dal[p]);
         acc0[p] = acc1[p] = acc2[p] = accd[p] = splat2(0.f);
     }
 #pragma unroll
@@ -1064,14 +1072,15 @@ using namespace fdgs;
 
 namespace fdgs {
 int render_fwd_impl(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, void* img, uint32_t R, float* out_color,
-                    float* out_depth, bool order_made) {
+                    float* out_depth, bool order_made, float* out_alpha) {
     int rc = validate_raster_params(p);
     if (rc) return rc;
     FDGS_REQUIRE(geom && img && out_color && out_depth && (binning || R == 0), "NULL buffer");
+    FDGS_REQUIRE(aligned_to(out_alpha, 4), "out_alpha must be 4-byte aligned");
     hipStream_t stream = (hipStream_t)stream_;
     RenderArgs a{};
     const ImgLayout il = fill_blend_args(a, p, geom, binning, img, R);
-    a.out_color = out_color; a.out_depth = out_depth;
+    a.out_color = out_color; a.out_depth = out_depth; a.out_alpha = out_alpha;
     a.tile_todo = at<uint32_t>(img, il.todo);
     a.zfill = reinterpret_cast<float4*>(p->acc_zero); a.zfill_n4 = (uint32_t)p->P * 4u;
     a.order = R == 0 ? nullptr : order_made ? at<uint32_t>(img, il.order_f) : make_tile_order(stream, 0, il, img, img);
@@ -1086,7 +1095,12 @@ int render_fwd_impl(void* stream_, const fdgs_raster_params* p, const void* geom
 
 extern "C" int fdgs_render_fwd(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, void* img,
                                uint32_t R, float* out_color, float* out_depth) {
-    return render_fwd_impl(stream_, p, geom, binning, img, R, out_color, out_depth, false);
+    return render_fwd_impl(stream_, p, geom, binning, img, R, out_color, out_depth, false, nullptr);
+}
+
+extern "C" int fdgs_render_fwd_alpha(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, void* img,
+                                     uint32_t R, float* out_color, float* out_depth, float* out_alpha) {
+    return render_fwd_impl(stream_, p, geom, binning, img, R, out_color, out_depth, false, out_alpha);
 }
 
 extern "C" int fdgs_render_pick(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
@@ -1180,11 +1194,14 @@ extern "C" int fdgs_render_contrib(void* stream_, const fdgs_raster_params* p, c
     return FDGS_OK;
 }
 
-extern "C" int fdgs_raster_bwd(void* stream_,const fdgs_raster_params* p, const void* geom, const void* binning,
-                               const void* img, uint32_t R, const fdgs_raster_grads* g) {
+// fdgs_raster_bwd (dL_dalpha == nullptr) and fdgs_raster_bwd_alpha
+static int raster_bwd_impl(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img, uint32_t R,
+                           const fdgs_raster_grads* g, const float* dL_dalpha) {
     int rc = validate_raster_params(p);
     if (rc) return rc;
     FDGS_REQUIRE(g && geom && img && (binning || R == 0), "NULL buffer");
+    FDGS_REQUIRE(aligned_to(dL_dalpha, 4), "dL_dalpha must be 4-byte aligned");
+    if (p->P == 0) return FDGS_OK;      // an empty set: no row to write (its optional per-row inputs may come without their gradient buffers)
     if (g->deform_epilogue) {     // the per-Gaussian results go to the deformation backward's buffers instead (include/fdgs.h)
         FDGS_REQUIRE(g->dL_dcolor && g->dL_dmeans2D && g->scratch_acc, "required gradient buffer is NULL");
     } else {
@@ -1195,7 +1212,6 @@ extern "C" int fdgs_raster_bwd(void* stream_,const fdgs_raster_params* p, const 
     }
     hipStream_t stream = (hipStream_t)stream_;
     const size_t P = (size_t)p->P;
-    if (P == 0) return FDGS_OK;
     // the per-Gaussian outputs are written for every Gaussian by preprocess_bwd; only the atomic accumulator needs zeros
     if (!g->scratch_acc_zeroed) FDGS_HIP_CHECK(hipMemsetAsync(g->scratch_acc, 0, P * 64, stream));      // (1: the forward filled it, fdgs_raster_params::acc_zero)
     if (p->cov3D_precomp) {   // scale/rotation gradients do not exist on this path: hand back zeros if buffers were given
@@ -1205,7 +1221,7 @@ extern "C" int fdgs_raster_bwd(void* stream_,const fdgs_raster_params* p, const 
     if (R > 0) {
         RenderBwdArgs a{};
         const ImgLayout il = fill_blend_args(a, p, geom, binning, img, R);
-        a.dL_dcolor = g->dL_dcolor; a.dL_ddepth = g->dL_ddepth;
+        a.dL_dcolor = g->dL_dcolor; a.dL_ddepth = g->dL_ddepth; a.dL_dalpha = dL_dalpha;
         a.gacc = g->scratch_acc;
         // (the order lists live in `img`, the forward's state, which this call otherwise only reads: the slice written here is scratch of the
         // backward that belongs to this frame -- one backward per forward state at a time, as for every other buffer of the state)
@@ -1220,4 +1236,14 @@ extern "C" int fdgs_raster_bwd(void* stream_,const fdgs_raster_params* p, const 
         FDGS_LAUNCH_CHECK("render_bwd", p->debug, stream);
     }
     return fdgs_launch_preprocess_bwd(stream, p, geom, g);
+}
+
+extern "C" int fdgs_raster_bwd(void* stream_,const fdgs_raster_params* p, const void* geom, const void* binning,
+                               const void* img, uint32_t R, const fdgs_raster_grads* g) {
+    return raster_bwd_impl(stream_, p, geom, binning, img, R, g, nullptr);
+}
+
+extern "C" int fdgs_raster_bwd_alpha(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning,
+                                     const void* img, uint32_t R, const fdgs_raster_grads* g, const float* dL_dalpha) {
+    return raster_bwd_impl(stream_, p, geom, binning, img, R, g, dL_dalpha);
 }

@@ -8,6 +8,7 @@ merge_many_4dgs.py:33,85-135 and scene/dataset_readers.py:485-508:
     GaussianRasterizer(raster_settings)(means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
                                         rotations=None, cov3D_precomp=None) -> (color [3,H,W], radii [P] int32,
                                                                                 depth [1,H,W])
+    GaussianRasterizer(raster_settings, render_alpha=True)(...) -> (color, radii, depth, alpha [1,H,W])      # opt-in, differentiable
     GaussianRasterizer.markVisible(positions) -> bool [P]
 
 All arithmetic runs in libfdgs.so (hand-written HIP for gfx950) through the C-ABI of include/fdgs.h; PyTorch only
@@ -162,7 +163,7 @@ def _none_if_empty(t):
 class RasterState:
     """Buffers one forward pass leaves behind for its backward (the reference's geom/binning/img buffers).  `capacity` = the pair count
     the binning buffer is laid out for (what the C calls take as num_rendered); `num_rendered` = the true count (waits for it if needed)."""
-    __slots__ = ("params", "geom", "binning", "img", "capacity", "count", "keep", "visibility", "acc")
+    __slots__ = ("params", "geom", "binning", "img", "capacity", "count", "keep", "visibility", "acc", "with_alpha")
 
     def take_accumulator(self):
         """(buffer, zeroed) for fdgs_raster_grads::scratch_acc: the [P,16] accumulator the forward zero-filled on the way (training frames), once;
@@ -224,19 +225,26 @@ def _claim_count(dev, key, P):
     return cnt, seen, pending
 
 
-def _finish_exact(L, st, p, geom, img, cnt, color, depth):
-    """Stages 3-4 on a binning buffer of the true size, cnt.R pairs (stages 1-2 are complete in `geom`) -> (binning, cnt.R)."""
+def _finish_exact(L, st, p, geom, img, cnt, color, depth, alpha=None):
+    """Stages 3-4 on a binning buffer of the true size, cnt.R pairs (stages 1-2 are complete in `geom`) -> (binning, cnt.R).  `alpha`: the
+    frame asked for its accumulated opacity (the blend writes that image too)."""
     binning = torch.empty(_bytes(L, "binning", cnt.R, p.W, p.H), dtype=torch.uint8, device=geom.device)
     check(L.fdgs_bin_sort(st, p, ptr(geom), ptr(binning), ptr(img), cnt.R))
-    check(L.fdgs_render_fwd(st, p, ptr(geom), ptr(binning), ptr(img), cnt.R, ptr(color), ptr(depth)))
+    if alpha is None:
+        check(L.fdgs_render_fwd(st, p, ptr(geom), ptr(binning), ptr(img), cnt.R, ptr(color), ptr(depth)))
+    else:
+        check(L.fdgs_render_fwd_alpha(st, p, ptr(geom), ptr(binning), ptr(img), cnt.R, ptr(color), ptr(depth), ptr(alpha)))
     return binning, cnt.R
 
 
-def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, out=None, expect_backward=False):
+def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, out=None, expect_backward=False,
+                      want_alpha=False):
     """Runs stages 1-4 of include/fdgs.h. Returns (color, radii, depth, state).  `out` = (color [3,H,W], radii [P] int32, depth [1,H,W])
     buffers to write into (contiguous float32 / int32 on the device), e.g. slices of a batch tensor.  `expect_backward`: a training frame
     (the blending forward zero-fills the backward's accumulator on the way).  Which binning path runs: BINNING above -- every mode but the
-    opt-in "capacity" returns the exact path's image."""
+    opt-in "capacity" returns the exact path's image.  `want_alpha`: the frame also delivers its accumulated opacity 1 - final_T; the result
+    is then (color, radii, depth, alpha [1,H,W], state), `out` has the alpha buffer as its fourth entry and the backward of `state` runs
+    fdgs_raster_bwd_alpha (rasterize_backward's grad_alpha).  A frame that does not ask makes the C calls it always made."""
     global capacity_reruns
     L = _lib.lib()
     dev = means3D.device
@@ -246,8 +254,13 @@ def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales,
     P, W, H = p.P, p.W, p.H
     geom = torch.empty(_bytes(L, "geom", P), dtype=torch.uint8, device=dev)
     img = torch.empty(_bytes(L, "img", W, H), dtype=torch.uint8, device=dev)
-    color, radii, depth = out if out is not None else (torch.empty(3, H, W, dtype=torch.float32, device=dev),
-                                                       torch.empty(P, dtype=torch.int32, device=dev), torch.empty(1, H, W, dtype=torch.float32, device=dev))
+    if out is None:
+        out = (torch.empty(3, H, W, dtype=torch.float32, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
+               torch.empty(1, H, W, dtype=torch.float32, device=dev))
+        if want_alpha:
+            out += (torch.empty(1, H, W, dtype=torch.float32, device=dev),)
+    color, radii, depth = out[:3]
+    alpha = out[3] if want_alpha else None
     vis = torch.empty(P, dtype=torch.bool, device=dev)       # radii > 0, written by the projection kernel (no elementwise launch)
     p.visibility = ptr(vis)
     # a training frame: the blending forward zero-fills the backward's per-Gaussian accumulator on the way (no fill launch before the backward)
@@ -260,7 +273,11 @@ def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales,
         cap = (int(seen[0] * CAPACITY_SLACK) + 8192) // 4096 * 4096
         ctypes.c_uint32.from_address(cnt.addr).value = _SENTINEL
         binning = torch.empty(_bytes(L, "binning", cap, W, H), dtype=torch.uint8, device=dev)
-        check(L.fdgs_raster_fwd_capacity(st, p, ptr(geom), ptr(binning), ptr(img), cap, _lib.c_void_p(cnt.addr), ptr(radii), ptr(color), ptr(depth)))
+        if alpha is None:
+            check(L.fdgs_raster_fwd_capacity(st, p, ptr(geom), ptr(binning), ptr(img), cap, _lib.c_void_p(cnt.addr), ptr(radii), ptr(color), ptr(depth)))
+        else:
+            check(L.fdgs_raster_fwd_capacity_alpha(st, p, ptr(geom), ptr(binning), ptr(img), cap, _lib.c_void_p(cnt.addr), ptr(radii), ptr(color),
+                                                   ptr(depth), ptr(alpha)))
         if BINNING == "capacity":      # opt-in: never waits; the count is looked at when a later frame starts
             cnt.capacity = cap
             cnt.stream = _current_stream(dev)
@@ -272,17 +289,19 @@ def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales,
             _note_count(cnt)
             if cnt.R > cap:            # the speculative frame dropped pairs: finish it exactly
                 capacity_reruns += 1
-                binning, cap = _finish_exact(L, st, p, geom, img, cnt, color, depth)
+                binning, cap = _finish_exact(L, st, p, geom, img, cnt, color, depth, alpha)
     else:
         check(L.fdgs_preprocess_fwd(st, p, ptr(geom), ptr(radii)))
         check(L.fdgs_bin_prepare(st, p, ptr(geom), _lib.c_void_p(cnt.addr)))          # (blocks until the count is in host memory)
         cnt.R = ctypes.c_uint32.from_address(cnt.addr).value
         _note_count(cnt)
-        binning, cap = _finish_exact(L, st, p, geom, img, cnt, color, depth)
+        binning, cap = _finish_exact(L, st, p, geom, img, cnt, color, depth, alpha)
     _tls.st["last"] = cnt
     state = RasterState()
     state.params, state.geom, state.binning, state.img, state.capacity, state.count = p, geom, binning, img, cap, cnt
-    state.visibility, state.acc, state.keep = vis, acc, tensors
+    state.visibility, state.acc, state.keep, state.with_alpha = vis, acc, tensors, alpha is not None
+    if alpha is not None:
+        return color, radii, depth, alpha, state
     return color, radii, depth, state
 
 
@@ -296,6 +315,16 @@ def fill_raster_grads(state, grad_color, grad_depth, d_means2D, epilogue=None):
     if epilogue is not None:
         g.deform_epilogue = ctypes.pointer(epilogue)
     return g, acc
+
+
+def raster_bwd_call(L, state, g, grad_alpha=None):
+    """fdgs_raster_bwd of `state` on the filled fdgs_raster_grads `g`; a frame rendered with alpha (rasterize_forward's want_alpha) runs
+    fdgs_raster_bwd_alpha, with `grad_alpha` [1,H,W] (contiguous float32) or NULL where alpha did not reach the loss."""
+    if state.with_alpha:
+        check(L.fdgs_raster_bwd_alpha(stream_ptr(), state.params, ptr(state.geom), ptr(state.binning), ptr(state.img), state.capacity, g,
+                                      ptr(grad_alpha)))
+    else:
+        check(L.fdgs_raster_bwd(stream_ptr(), state.params, ptr(state.geom), ptr(state.binning), ptr(state.img), state.capacity, g))
 
 
 def camera_wants_grad(settings):
@@ -323,14 +352,17 @@ def split_camera_gradients(out48, viewmatrix, projmatrix, campos):
     return like(out48[:16], viewmatrix), like(out48[16:32], projmatrix), like(out48[32:35], campos)
 
 
-def rasterize_backward(state, grad_color, grad_depth=None, camera=False):
+def rasterize_backward(state, grad_color, grad_depth=None, camera=False, grad_alpha=None):
     """Backward of rasterize_forward. Returns dict of gradients (None where the input was absent).  `camera`: also the camera's gradient,
-    as `viewmatrix` [4,4], `projmatrix` [4,4] and `campos` [3] (fdgs_camera_grad on the same accumulator, behind fdgs_raster_bwd)."""
+    as `viewmatrix` [4,4], `projmatrix` [4,4] and `campos` [3] (fdgs_camera_grad on the same accumulator, behind fdgs_raster_bwd).
+    `grad_alpha`: the gradient of the alpha image of a frame rendered with want_alpha (None: it did not reach the loss)."""
     L = _lib.lib()
     p = state.params
     means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp = state.keep[:7]
     dev, P = means3D.device, p.P
-    grad_color, grad_depth = _f32(grad_color, dev), _f32(grad_depth, dev)
+    grad_color, grad_depth, grad_alpha = _f32(grad_color, dev), _f32(grad_depth, dev), _f32(grad_alpha, dev)
+    if grad_alpha is not None and not state.with_alpha:
+        raise _lib.FdgsError("grad_alpha for a frame that was rendered without alpha (rasterize_forward's want_alpha)")
     out = dict(means2D=torch.empty(P, 3, device=dev), means3D=torch.empty(P, 3, device=dev),
                opacities=torch.empty(P, 1, device=dev), colors=torch.empty(P, 3, device=dev),
                cov3D=torch.empty(P, 6, device=dev),
@@ -340,18 +372,32 @@ def rasterize_backward(state, grad_color, grad_depth=None, camera=False):
     g, scratch = fill_raster_grads(state, grad_color, grad_depth, out["means2D"])
     g.dL_dmeans3D, g.dL_dopacity, g.dL_dcolors, g.dL_dcov3D = ptr(out["means3D"]), ptr(out["opacities"]), ptr(out["colors"]), ptr(out["cov3D"])
     g.dL_dsh, g.dL_dscales, g.dL_drotations = ptr(out["shs"]), ptr(out["scales"]), ptr(out["rotations"])
-    check(L.fdgs_raster_bwd(stream_ptr(), p, ptr(state.geom), ptr(state.binning), ptr(state.img), state.capacity, g))
+    raster_bwd_call(L, state, g, grad_alpha)
     if camera:
         c = out["camera"] = camera_gradients(state, scratch)       # (the call's 48 floats; the three below are views of it)
         out.update(viewmatrix=c[:16].reshape(4, 4), projmatrix=c[16:32].reshape(4, 4), campos=c[32:35])
     return out
 
 
+def _image_grads(state, grad_color, grad_depth, grad_alpha):
+    """(dL_dcolor, keywords of rasterize_backward) of a node's backward, or None where no image reached the loss.  A loss that saw depth or
+    alpha but not the colour gets a zero colour image; a frame without alpha passes the keywords it always passed."""
+    if grad_color is None:
+        if grad_depth is None and grad_alpha is None:
+            return None
+        like = grad_depth if grad_depth is not None else grad_alpha
+        grad_color = torch.zeros(3, state.params.H, state.params.W, device=like.device)
+    return grad_color, ({"grad_alpha": grad_alpha} if getattr(state, "with_alpha", False) else {})
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_mode=True):
-        color, radii, depth, state = rasterize_forward(raster_settings, means3D, sh, colors_precomp, opacities, scales,
-                                                       rotations, cov3Ds_precomp, expect_backward=bool(grad_mode) and any(ctx.needs_input_grad))
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_mode=True,
+                want_alpha=False):
+        *images, state = rasterize_forward(raster_settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                           expect_backward=bool(grad_mode) and any(ctx.needs_input_grad),
+                                           **({"want_alpha": True} if want_alpha else {}))
+        radii = images[1]
         ctx.state = state
         ctx.had = (sh is not None and sh.numel() > 0, colors_precomp is not None and colors_precomp.numel() > 0,
                    scales is not None and scales.numel() > 0, cov3Ds_precomp is not None and cov3Ds_precomp.numel() > 0)
@@ -361,20 +407,19 @@ class _RasterizeGaussians(torch.autograd.Function):
         # reference's training loss ignores `depth` (train.py:201-214), and a NULL dL_ddepth selects the blending
         # backward without the depth terms (render_bwd_kernel<false>, csrc/render.hip)
         ctx.set_materialize_grads(False)
-        return color, radii, depth
+        return tuple(images)        # (color, radii, depth) and, where asked for, alpha
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_depth):
-        if grad_color is None:
-            if grad_depth is None:      # neither image reached the loss
-                return (None,) * 10
-            grad_color = torch.zeros(3, ctx.state.params.H, ctx.state.params.W, device=grad_depth.device)
-        g = rasterize_backward(ctx.state, grad_color, grad_depth)
+    def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha=None):
+        grads = _image_grads(ctx.state, grad_color, grad_depth, grad_alpha)
+        if grads is None:               # no image reached the loss
+            return (None,) * 11
+        g = rasterize_backward(ctx.state, grads[0], grad_depth, **grads[1])
         had_sh, had_col, had_scale, had_cov = ctx.had
         op_shape, sh_shape = ctx.shapes
         return (g["means3D"], g["means2D"], g["shs"].reshape(sh_shape) if had_sh else None, g["colors"] if had_col else None,
                 g["opacities"].reshape(op_shape), g["scales"] if had_scale else None, g["rotations"] if had_scale else None,
-                g["cov3D"] if had_cov else None, None, None)
+                g["cov3D"] if had_cov else None, None, None, None)
 
 
 class _RasterizeGaussiansCamera(torch.autograd.Function):
@@ -384,9 +429,10 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix, campos,
-                raster_settings):
-        color, radii, depth, state = rasterize_forward(raster_settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                                       expect_backward=True)
+                raster_settings, want_alpha=False):
+        *images, state = rasterize_forward(raster_settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                           expect_backward=True, **({"want_alpha": True} if want_alpha else {}))
+        radii = images[1]
         ctx.state = state
         ctx.had = (sh is not None and sh.numel() > 0, colors_precomp is not None and colors_precomp.numel() > 0,
                    scales is not None and scales.numel() > 0, cov3Ds_precomp is not None and cov3Ds_precomp.numel() > 0)
@@ -394,37 +440,40 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
         ctx.cam = (viewmatrix, projmatrix, campos)        # (shape / dtype / device of the gradients to return; inputs of this node anyway)
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)
-        return color, radii, depth
+        return tuple(images)
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_depth):
-        if grad_color is None:
-            if grad_depth is None:
-                return (None,) * 12
-            grad_color = torch.zeros(3, ctx.state.params.H, ctx.state.params.W, device=grad_depth.device)
-        g = rasterize_backward(ctx.state, grad_color, grad_depth, camera=True)
+    def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha=None):
+        grads = _image_grads(ctx.state, grad_color, grad_depth, grad_alpha)
+        if grads is None:
+            return (None,) * 13
+        g = rasterize_backward(ctx.state, grads[0], grad_depth, camera=True, **grads[1])
         had_sh, had_col, had_scale, had_cov = ctx.had
         op_shape, sh_shape = ctx.shapes
         cam = split_camera_gradients(g["camera"], *ctx.cam)
         return (g["means3D"], g["means2D"], g["shs"].reshape(sh_shape) if had_sh else None, g["colors"] if had_col else None,
                 g["opacities"].reshape(op_shape), g["scales"] if had_scale else None, g["rotations"] if had_scale else None,
-                g["cov3D"] if had_cov else None, *cam, None)
+                g["cov3D"] if had_cov else None, *cam, None, None)
 
 
-def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, render_alpha=False):
+    """-> (color, radii, depth), with `render_alpha` (color, radii, depth, alpha)."""
     if camera_wants_grad(raster_settings):
         rs = raster_settings
         return _RasterizeGaussiansCamera.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                               rs.viewmatrix, rs.projmatrix, rs.campos, rs)
+                                               rs.viewmatrix, rs.projmatrix, rs.campos, rs, bool(render_alpha))
     # (grad mode is read HERE: inside autograd.Function.forward it is always off and needs_input_grad stays True under torch.no_grad())
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                     raster_settings, torch.is_grad_enabled())
+                                     raster_settings, torch.is_grad_enabled(), bool(render_alpha))
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings):
+    def __init__(self, raster_settings, render_alpha=False):
+        """`render_alpha`: forward also returns the accumulated opacity of every pixel, alpha [1,H,W] = 1 - final transmittance,
+        differentiable like colour and depth -> (color, radii, depth, alpha)."""
         super().__init__()
         self.raster_settings = raster_settings
+        self.render_alpha = bool(render_alpha)
 
     def markVisible(self, positions):
         L = _lib.lib()
@@ -444,4 +493,4 @@ class GaussianRasterizer(nn.Module):
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   self.raster_settings)
+                                   self.raster_settings, self.render_alpha)

@@ -1,6 +1,7 @@
 """Drop-in for `gaussian_renderer.render` of the reference (gaussian_renderer/__init__.py:18-138).
 
-Same signature, same result dict {"render","viewspace_points","visibility_filter","radii","depth"}; honours
+Same signature, same result dict {"render","viewspace_points","visibility_filter","radii","depth"} (and, opt-in through
+`pipe.render_alpha = True`, "alpha": the accumulated opacity [1,H,W], differentiable); honours
 pipe.convert_SHs_python / pipe.compute_cov3D_python / pipe.debug and cam_type == "PanopticSports" exactly where the
 reference does.  When `pc._deformation` is this package's `deform_network`, the fine stage runs as two fused HIP
 stages: deform(+activations, + the cat of features_dc/features_rest) -> rasterize; no `time.repeat(N,1)` tensor, no
@@ -95,9 +96,10 @@ def _fill_epilogue(st, b, assign):
     return epi
 
 
-def _fused_backward(states, saved, grad_colors, grad_depths, camera=None, **prepare):
+def _fused_backward(states, saved, grad_colors, grad_depths, camera=None, grad_alphas=None, **prepare):
     """The backward of the fused fine stage for the views of one autograd node: states = [(deformation state, raster state)], saved = their
-    (o_sc, o_rot, o_op) in a row, grad_colors / grad_depths = the per-view image gradients (or None), `prepare` goes to backward_prepare.
+    (o_sc, o_rot, o_op) in a row, grad_colors / grad_depths / grad_alphas = the per-view image gradients (or None; alpha: frames rendered
+    with it), `prepare` goes to backward_prepare.
     Last view first (its saved activations, lists and records are the ones still partly resident in the 256 MB Infinity Cache), per view: the
     rasterizer backward, whose epilogue writes into the ONE gradient arena (the first processed view assigns the identity paths, later ones
     accumulate), then that view's deformation backward -- same output pointers and scratch (stream-ordered reuse), its own saved activations.
@@ -113,10 +115,11 @@ def _fused_backward(states, saved, grad_colors, grad_depths, camera=None, **prep
         p = rstate.params
         gc = _lib.f32(grad_colors[v]) if grad_colors is not None else torch.zeros(3, p.H, p.W, device=dev)
         gd = _lib.f32(grad_depths[v]) if grad_depths is not None else None
+        ga = _lib.f32(grad_alphas[v]) if grad_alphas is not None else None
         gm = g_means2D[v] = torch.empty(p.P, 3, device=dev)
         epi = _fill_epilogue(st, b, EPILOGUE_ASSIGN and k_ == 0)
         g, acc = _rasterizer.fill_raster_grads(rstate, gc, gd, gm, epi)      # (acc: zero-filled by the blending forward of this frame, no fill launch here)
-        _lib.check(L.fdgs_raster_bwd(stream, p, _lib.ptr(rstate.geom), _lib.ptr(rstate.binning), _lib.ptr(rstate.img), rstate.capacity, g))
+        _rasterizer.raster_bwd_call(L, rstate, g, ga)
         if camera is not None:
             camera.append(_rasterizer.camera_gradients(rstate, acc))
         b.g.out_scales, b.g.out_rotations, b.g.out_opacity = _lib.ptr(saved[3 * v]), _lib.ptr(saved[3 * v + 1]), _lib.ptr(saved[3 * v + 2])
@@ -124,8 +127,17 @@ def _fused_backward(states, saved, grad_colors, grad_depths, camera=None, **prep
         b.g.packed_rows_ready = epi.tile_flags + 1
         _lib.check(L.fdgs_deform_bwd(stream, st.p, b.g))
         _deformation.note_live_tiles(st, b)
-        keep.append((gc, gd, acc, epi))      # (what the queued launches read lives until the last of them is queued)
+        keep.append((gc, gd, ga, acc, epi))      # (what the queued launches read lives until the last of them is queued)
     return g_means2D, _deformation.gradient_tuple(st0, b)      # ([d means2D per view], the arena's views in _DeformFunction's input order)
+
+
+def _alpha_kw(cfg):
+    """rasterize_forward's keyword of a frame that asked for its alpha image (cfg["alpha"], from pipe.render_alpha); nothing otherwise."""
+    return {"want_alpha": True} if cfg.get("alpha") else {}
+
+
+def _wants_alpha(pipe):
+    return bool(getattr(pipe, "render_alpha", False))
 
 
 class _FusedRenderFunction(torch.autograd.Function):
@@ -133,24 +145,26 @@ class _FusedRenderFunction(torch.autograd.Function):
     def forward(ctx, cfg, t_scalar, raster_settings, means2D, xyz, scales, rotations, opacity, sh_a, sh_b, aabb, *rest):
         st = _deformation.forward_impl(cfg, t_scalar, xyz, scales, rotations, opacity, sh_a, sh_b, None, aabb, rest,
                                        any(ctx.needs_input_grad))
-        color, radii, depth, rstate = _rasterizer.rasterize_forward(raster_settings, st.o_xyz, st.o_sh, None, st.o_op, st.o_sc, st.o_rot, None,
-                                                                    expect_backward=bool(cfg.get("grad")) and any(ctx.needs_input_grad))
+        color, radii, depth, *alpha, rstate = _rasterizer.rasterize_forward(raster_settings, st.o_xyz, st.o_sh, None, st.o_op, st.o_sc, st.o_rot, None,
+                                                                            expect_backward=bool(cfg.get("grad")) and any(ctx.needs_input_grad),
+                                                                            **_alpha_kw(cfg))
         ctx.st, ctx.rstate = st, rstate
         ctx.save_for_backward(st.o_sc, st.o_rot, st.o_op)       # (see _DeformFunction.forward: no reference cycle through ctx)
         st.o_xyz = st.o_sc = st.o_rot = st.o_op = st.o_sh = None
         vis = rstate.visibility                                 # radii > 0, written by the projection kernel itself
         ctx.mark_non_differentiable(radii, vis)
         ctx.set_materialize_grads(False)
-        return color, radii, depth, vis
+        return (color, radii, depth, vis, *alpha)               # (alpha: where the frame asked, cfg["alpha"])
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_depth, grad_vis=None):
+    def backward(ctx, grad_color, grad_radii, grad_depth, grad_vis=None, grad_alpha=None):
         st = ctx.st
-        if grad_color is None and grad_depth is None:
+        if grad_color is None and grad_depth is None and grad_alpha is None:
             return (None,) * (11 + len(st.plane_shapes) + len(st.keep[0][8]))
         # one view; the epilogue kernel also clears the accumulate-into part of the arena on the way
         g_means2D, grads = _fused_backward([(st, ctx.rstate)], ctx.saved_tensors, None if grad_color is None else (grad_color,),
-                                           None if grad_depth is None else (grad_depth,), zero_by_epilogue=EPILOGUE_ASSIGN)
+                                           None if grad_depth is None else (grad_depth,), zero_by_epilogue=EPILOGUE_ASSIGN,
+                                           grad_alphas=None if grad_alpha is None else (grad_alpha,))
         return (None, None, None, *g_means2D) + grads[:6] + grads[7:]       # (grads[6]: the time tensor, no input here)
 
 
@@ -163,24 +177,25 @@ class _FusedRenderCameraFunction(torch.autograd.Function):
     def forward(ctx, cfg, t_scalar, raster_settings, viewmatrix, projmatrix, campos, means2D, xyz, scales, rotations, opacity, sh_a, sh_b, aabb,
                 *rest):
         st = _deformation.forward_impl(cfg, t_scalar, xyz, scales, rotations, opacity, sh_a, sh_b, None, aabb, rest, True)
-        color, radii, depth, rstate = _rasterizer.rasterize_forward(raster_settings, st.o_xyz, st.o_sh, None, st.o_op, st.o_sc, st.o_rot, None,
-                                                                    expect_backward=True)
+        color, radii, depth, *alpha, rstate = _rasterizer.rasterize_forward(raster_settings, st.o_xyz, st.o_sh, None, st.o_op, st.o_sc, st.o_rot, None,
+                                                                            expect_backward=True, **_alpha_kw(cfg))
         ctx.st, ctx.rstate, ctx.cam = st, rstate, (viewmatrix, projmatrix, campos)
         ctx.save_for_backward(st.o_sc, st.o_rot, st.o_op)
         st.o_xyz = st.o_sc = st.o_rot = st.o_op = st.o_sh = None
         vis = rstate.visibility
         ctx.mark_non_differentiable(radii, vis)
         ctx.set_materialize_grads(False)
-        return color, radii, depth, vis
+        return (color, radii, depth, vis, *alpha)
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_depth, grad_vis=None):
+    def backward(ctx, grad_color, grad_radii, grad_depth, grad_vis=None, grad_alpha=None):
         st = ctx.st
-        if grad_color is None and grad_depth is None:
+        if grad_color is None and grad_depth is None and grad_alpha is None:
             return (None,) * (14 + len(st.plane_shapes) + len(st.keep[0][8]))
         cam = []
         g_means2D, grads = _fused_backward([(st, ctx.rstate)], ctx.saved_tensors, None if grad_color is None else (grad_color,),
-                                           None if grad_depth is None else (grad_depth,), camera=cam, zero_by_epilogue=EPILOGUE_ASSIGN)
+                                           None if grad_depth is None else (grad_depth,), camera=cam, zero_by_epilogue=EPILOGUE_ASSIGN,
+                                           grad_alphas=None if grad_alpha is None else (grad_alpha,))
         return (None, None, None, *_rasterizer.split_camera_gradients(cam[0], *ctx.cam), *g_means2D) + grads[:6] + grads[7:]
 
 
@@ -200,11 +215,13 @@ class _FusedRenderViewsFunction(torch.autograd.Function):
         colors = torch.empty(nviews, 3, H, W, device=dev)          # every view renders straight into its slice
         radii_all = torch.empty(nviews, P, dtype=torch.int32, device=dev)
         depths = torch.empty(nviews, 1, H, W, device=dev)
+        alphas = torch.empty(nviews, 1, H, W, device=dev) if cfg.get("alpha") else None
         states = []
         for v in range(nviews):
             st = _deformation.forward_impl(cfg, times[v], xyz, scales, rotations, opacity, sh_a, sh_b, None, aabb, rest, want)
-            _, _, _, rstate = _rasterizer.rasterize_forward(settings_list[v], st.o_xyz, st.o_sh, None, st.o_op, st.o_sc, st.o_rot, None,
-                                                            out=(colors[v], radii_all[v], depths[v]), expect_backward=bool(cfg.get("grad")) and want)
+            out = (colors[v], radii_all[v], depths[v]) if alphas is None else (colors[v], radii_all[v], depths[v], alphas[v])
+            *_, rstate = _rasterizer.rasterize_forward(settings_list[v], st.o_xyz, st.o_sh, None, st.o_op, st.o_sc, st.o_rot, None,
+                                                       out=out, expect_backward=bool(cfg.get("grad")) and want, **_alpha_kw(cfg))
             st.o_xyz = st.o_sh = None
             states.append((st, rstate))
         ctx.states, ctx.nviews = states, nviews
@@ -214,14 +231,14 @@ class _FusedRenderViewsFunction(torch.autograd.Function):
             st.o_sc = st.o_rot = st.o_op = None
         ctx.mark_non_differentiable(radii_all)
         ctx.set_materialize_grads(False)
-        return colors, radii_all, depths
+        return (colors, radii_all, depths) if alphas is None else (colors, radii_all, depths, alphas)
 
     @staticmethod
-    def backward(ctx, grad_colors, grad_radii, grad_depths):
+    def backward(ctx, grad_colors, grad_radii, grad_depths, grad_alphas=None):
         st0 = ctx.states[0][0]
-        if grad_colors is None and grad_depths is None:
+        if grad_colors is None and grad_depths is None and grad_alphas is None:
             return (None,) * (4 + ctx.nviews + 7 + len(st0.plane_shapes) + len(st0.keep[0][8]))
-        g_means2D, grads = _fused_backward(ctx.states, ctx.saved_tensors, grad_colors, grad_depths)
+        g_means2D, grads = _fused_backward(ctx.states, ctx.saved_tensors, grad_colors, grad_depths, grad_alphas=grad_alphas)
         return (None, None, None, None, *g_means2D) + grads[:6] + grads[7:]
 
 
@@ -241,11 +258,16 @@ def render_views(viewpoint_cameras, pc, pipe, bg_color, scaling_modifier=1.0, st
         return [render(c, pc, pipe, bg_color, scaling_modifier, None, stage, cam_type) for c in cams]
     sinks = [_zero_leaf(means3D) for _ in cams]
     cfg, perm, ins, net_ins = _fine_stage(pc, sinks)       # (the set in Hilbert order for this step where perm is not None)
-    colors, radii, depths = _FusedRenderViewsFunction.apply(cfg, times, settings, len(cams), *ins, *net_ins)
+    if _wants_alpha(pipe):
+        cfg["alpha"] = True
+    colors, radii, depths, *alphas = _FusedRenderViewsFunction.apply(cfg, times, settings, len(cams), *ins, *net_ins)
     if perm is not None:
         radii = torch.stack(_deformation.permute_rows(perm, [radii[v] for v in range(len(cams))], scatter=True))
-    return [{"render": colors[v], "viewspace_points": sinks[v], "visibility_filter": radii[v] > 0, "radii": radii[v], "depth": depths[v]}
-            for v in range(len(cams))]
+    res = [{"render": colors[v], "viewspace_points": sinks[v], "visibility_filter": radii[v] > 0, "radii": radii[v], "depth": depths[v]}
+           for v in range(len(cams))]
+    for v, r in enumerate(res if alphas else ()):
+        r["alpha"] = alphas[0][v]
+    return res
 
 
 _zero_pool = {}
@@ -283,27 +305,33 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     # a leaf's .grad is filled by AccumulateGrad directly (same values, same attribute, read the same way by the train loop)
     screenspace_points = _zero_leaf(means3D)
     raster_settings, frame_time = _frame_settings(viewpoint_camera, cam_type, bg_color, scaling_modifier, pc.active_sh_degree, device, pipe)
+    want_alpha = _wants_alpha(pipe)          # opt-in: "alpha" [1,H,W], the accumulated opacity, joins the result (differentiable)
     if ("fine" in stage and "coarse" not in stage and FUSED_BACKWARD and override_color is None and not pipe.compute_cov3D_python
             and not pipe.convert_SHs_python and isinstance(pc._deformation, _deformation.deform_network)):
         # deformation + rasterizer as one autograd node (see _FusedRenderFunction)
         cfg, perm, ins, net_ins = _fine_stage(pc, (screenspace_points,) if torch.is_grad_enabled() else ())
+        if want_alpha:
+            cfg["alpha"] = True
         if cfg["grad"] and _rasterizer.camera_wants_grad(raster_settings):
             rs = raster_settings
-            rendered_image, radii, depth, vis = _FusedRenderCameraFunction.apply(cfg, frame_time, rs, rs.viewmatrix, rs.projmatrix, rs.campos,
-                                                                                 *ins, *net_ins)
+            rendered_image, radii, depth, vis, *alpha = _FusedRenderCameraFunction.apply(cfg, frame_time, rs, rs.viewmatrix, rs.projmatrix, rs.campos,
+                                                                                         *ins, *net_ins)
         elif cfg["grad"]:
-            rendered_image, radii, depth, vis = _FusedRenderFunction.apply(cfg, frame_time, raster_settings, *ins, *net_ins)
+            rendered_image, radii, depth, vis, *alpha = _FusedRenderFunction.apply(cfg, frame_time, raster_settings, *ins, *net_ins)
         else:
             # no graph will be recorded (render.py:57-70, evaluation): the two stages called directly -- autograd.Function.apply costs
             # 0.05 ms per frame for its 46 inputs even when it has nothing to record
             st = _deformation.forward_impl(cfg, frame_time, *ins, None, net_ins[0], net_ins[1:], False)
-            rendered_image, radii, depth, rstate = _rasterizer.rasterize_forward(raster_settings, st.o_xyz, st.o_sh, None, st.o_op, st.o_sc,
-                                                                                 st.o_rot, None, expect_backward=False)
+            rendered_image, radii, depth, *alpha, rstate = _rasterizer.rasterize_forward(raster_settings, st.o_xyz, st.o_sh, None, st.o_op, st.o_sc,
+                                                                                         st.o_rot, None, expect_backward=False, **_alpha_kw(cfg))
             vis = rstate.visibility
         if perm is not None:       # (radii and visibility back in the model's own row order)
             radii, = _deformation.permute_rows(perm, [radii], scatter=True)
             vis = radii > 0
-        return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": vis, "radii": radii, "depth": depth}
+        res = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": vis, "radii": radii, "depth": depth}
+        if alpha:
+            res["alpha"] = alpha[0]
+        return res
 
     means2D = screenspace_points
     opacity = pc._opacity
@@ -350,9 +378,12 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         colors_precomp = override_color
         shs_final = None
 
-    rasterizer = GaussianRasterizer(raster_settings=raster_settings)       # (an nn.Module: only built on the paths that call it)
-    rendered_image, radii, depth = rasterizer(
+    rasterizer = GaussianRasterizer(raster_settings=raster_settings, render_alpha=want_alpha)       # (an nn.Module: only built on the paths that call it)
+    rendered_image, radii, depth, *alpha = rasterizer(
         means3D=means3D_final, means2D=means2D, shs=shs_final, colors_precomp=colors_precomp, opacities=opacity_final,
         scales=scales_final, rotations=rotations_final, cov3D_precomp=cov3D_precomp)
-    return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-            "radii": radii, "depth": depth}
+    res = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
+           "radii": radii, "depth": depth}
+    if alpha:
+        res["alpha"] = alpha[0]
+    return res

@@ -139,6 +139,25 @@ int fdgs_pair_count_wait(void* stream, const uint32_t* num_rendered_host, uint32
 int fdgs_render_fwd(void* stream, const fdgs_raster_params* p, const void* geom, const void* binning, void* img,
                     uint32_t num_rendered, float* out_color, float* out_depth);
 
+/* Accumulated opacity (alpha) of a frame, differentiable.  A[y, x] = 1 - T_final = sum_i alpha_i T_i over the entries the pixel blended:
+ * what the blend leaves of a background of ones, the coverage a mask / silhouette loss, an opacity regulariser, a composite over a background
+ * IMAGE (render with bg = 0, then render + (1 - A) * B) or a normalised depth (depth / A) needs.
+ *   Forward: fdgs_render_fwd_alpha and fdgs_raster_fwd_capacity_alpha are fdgs_render_fwd and fdgs_raster_fwd_capacity with one more image,
+ *   out_alpha [H*W] floats (4-byte aligned): 1.0f - T of the very T the kernel stores per pixel for the backward, one more store where the
+ *   pixel's results are written.  A pixel with an empty list gets exactly 0; P = 0 or no pairs: all zeros.  out_alpha = NULL is the old call
+ *   (the old entry points are that case of the same implementation).
+ *   Backward: fdgs_raster_bwd_alpha is fdgs_raster_bwd with dL_dalpha [H*W] floats (4-byte aligned), the gradient of the loss to A.  Every
+ *   blended entry i of a pixel gets dL/dalpha_i += dL_dalpha * T_final / (1 - alpha_i) -- the background term's factor with the sign turned,
+ *   so the blending backward forms its per-pixel background term from (bg . dL_dcolor - dL_dalpha) and walks the lists as before: nothing
+ *   per list entry is added.  Entries behind the pixel's stop (T (1 - alpha) < 1e-4) get nothing and the 0.99 clamp of alpha is
+ *   straight-through, both as for colour.  Everything behind the blending backward -- the conic, mean2D and opacity sums, dL_dmeans2D, the
+ *   live-row flags, the deformation epilogue, fdgs_camera_grad on the same scratch_acc -- includes alpha's share by construction.
+ *   dL_dalpha = NULL is the old call.  A loss on alpha alone passes a zero dL_dcolor (it stays required). */
+int fdgs_render_fwd_alpha(void* stream, const fdgs_raster_params* p, const void* geom, const void* binning, void* img,
+                          uint32_t num_rendered, float* out_color, float* out_depth, float* out_alpha);
+int fdgs_raster_fwd_capacity_alpha(void* stream, const fdgs_raster_params* p, void* geom, void* binning, void* img, uint32_t capacity,
+                                   uint32_t* num_rendered_host, int32_t* radii, float* out_color, float* out_depth, float* out_alpha);
+
 /* Optional epilogue of fdgs_raster_bwd for the fused render() path (deformation -> rasterizer): the per-Gaussian chain rule
  * writes its results straight in the form fdgs_deform_bwd consumes -- the packed pre-activation output-gradient rows G[Npad][64]
  * (columns 0-2 position, 3-5 log-scale, 6-9 raw quaternion, 10 opacity logit, 16-63 SH; activation Jacobians of
@@ -197,6 +216,9 @@ typedef struct fdgs_raster_grads {
 /* Backward of stages 4 and 1 (back-to-front blending gradients, then per-Gaussian chain rule). */
 int fdgs_raster_bwd(void* stream, const fdgs_raster_params* p, const void* geom, const void* binning,
                     const void* img, uint32_t num_rendered, const fdgs_raster_grads* g);
+/* ... with the gradient of the accumulated opacity (see fdgs_render_fwd_alpha above); dL_dalpha opt [H*W] */
+int fdgs_raster_bwd_alpha(void* stream, const fdgs_raster_params* p, const void* geom, const void* binning,
+                          const void* img, uint32_t num_rendered, const fdgs_raster_grads* g, const float* dL_dalpha);
 
 /* Frustum test only (replaces _C.mark_visible): present[P] (uint8) = 1 where p_view.z > 0.2. */
 int fdgs_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
@@ -255,7 +277,8 @@ int fdgs_camera_grad_host(const fdgs_raster_params* p, const uint32_t* tiles, co
  * (what the motion pass does: fdgs_motion_rows writes straight into recC).  The second call must get the same geom, binning and img and
  * the num_rendered the buffers were laid out for; it gets its own out_color and a background of zeros (a copy of the params whose bg
  * points at three device zeros and whose acc_zero is NULL).  It leaves final_T, n_contrib, the ranges and the tile order as they were --
- * those decisions do not depend on colour -- and writes to out_depth the depth the first call wrote. */
+ * those decisions do not depend on colour -- and writes to out_depth the depth the first call wrote.  A second fdgs_render_fwd does not
+ * touch an alpha image the first call wrote (fdgs_render_fwd_alpha); a second fdgs_render_fwd_alpha writes the same alpha again. */
 int fdgs_geom_field(void* geom, int P, int which, void** ptr);
 /* 0 sorted pair Gaussian ids u32[R]; 1 sorted pair tile ids u32[R]. */
 int fdgs_binning_field(void* binning, uint32_t num_rendered, int W, int H, int which, void** ptr);
