@@ -158,6 +158,11 @@ SYMBOLS = {
     "fdgs_deform_bwd_live_tiles": (c_int, [c_void_p, POINTER(DeformParams), c_void_p, POINTER(c_uint32)]),
     "fdgs_hexplane_cells": (c_int, [c_void_p, POINTER(DeformParams), c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdgs_hexplane_cells_host": (c_int, [POINTER(DeformParams), c_void_p, c_void_p, c_void_p, c_void_p]),
+    # dL/dt behind a finished fdgs_deform_bwd (opt-in), its probe and its host twin
+    "fdgs_deform_time_grad_scratch_bytes": (c_int, [POINTER(DeformParams), POINTER(c_size_t)]),
+    "fdgs_deform_time_grad": (c_int, [c_void_p, POINTER(DeformParams), POINTER(DeformGrads), c_void_p, c_void_p]),
+    "fdgs_deform_time_grad_dfeat": (c_int, [c_void_p, POINTER(DeformParams), POINTER(DeformGrads), c_void_p, c_void_p]),
+    "fdgs_deform_time_grad_host": (c_int, [POINTER(DeformParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdgs_l1_stats": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
     "fdgs_l1_stats_scratch_bytes": (c_int, [POINTER(c_size_t)]),
     "fdgs_l1_stats_assign": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),

@@ -8,6 +8,10 @@ per camera, zero = the camera as it is.  The chain from the three tensors' gradi
     opt = torch.optim.Adam(delta.parameters(), lr=1e-3)
     out = render(delta.pose(cam), gaussians, pipe, background)         # or GaussianRasterizer(delta.settings(...)) for the raw route
     loss(out["render"], target).backward()                             # model and pose gradients from the same backward
+
+The frame time is the other thing a camera can be wrong about.  render() and deform() return dL/dt when the time is a tensor that requires
+grad (csrc/deform_time_grad.h, fdgs_deform_time_grad); `TimeDelta` is the parametrisation in front of it: one offset per camera, zero = the
+camera's own time.  The two compose: `TimeDelta.camera(PoseDelta.pose(cam))` is a camera whose pose and time are both being fitted.
 """
 import torch
 import torch.nn as nn
@@ -68,3 +72,23 @@ class PoseDelta(nn.Module):
         """The raw route: a GaussianRasterizationSettings whose viewmatrix, projmatrix and campos are this correction's."""
         V, F, c = self.transforms(raster_settings.viewmatrix, raster_settings.projmatrix)
         return raster_settings._replace(viewmatrix=V, projmatrix=F, campos=c)
+
+
+class TimeDelta(nn.Module):
+    """A time offset per camera: cameras that are not frame-synchronised, jittered timestamps, or "when was this photo taken" against a
+    frozen model.  `offset` [n_cameras], zero = the camera's own time."""
+
+    def __init__(self, n_cameras=1, dtype=torch.float32):
+        super().__init__()
+        self.offset = nn.Parameter(torch.zeros(n_cameras, dtype=dtype))
+
+    def camera(self, camera, index=0):
+        """`camera` (anything with the fields render() reads, a PosedCamera of PoseDelta.pose included) at time + offset[index] ->
+        PosedCamera whose `time` is a 0-dim tensor that carries the graph; everything else is the camera's own."""
+        t = camera.time
+        if not isinstance(t, torch.Tensor):
+            t = torch.tensor(float(t), dtype=self.offset.dtype, device=self.offset.device)
+        time = t.to(device=self.offset.device, dtype=self.offset.dtype).reshape(()) + self.offset[index]
+        return PosedCamera(image_height=camera.image_height, image_width=camera.image_width, FoVx=camera.FoVx, FoVy=camera.FoVy, time=time,
+                           world_view_transform=camera.world_view_transform, full_proj_transform=camera.full_proj_transform,
+                           camera_center=camera.camera_center, projection_matrix=getattr(camera, "projection_matrix", None))

@@ -29,7 +29,7 @@
 //      over after the last full round of its persistent loop out by head (FDGS_D1_SPLIT).
 // This file is the host side only: validation, the layouts of the caller's buffers, one launch plan per pass and the C ABI.  The kernels are
 // the headers included below: deform_layers.h (MFMA wrappers, HexPlane sampling, DeformDev, the dense-layer blocks), deform_fwd32.h / _fwd16.h /
-// _fwd_ws.h (D1, three forms), hexplane_ops.h (the index arithmetic of the HexPlane lookup, host/device, contraction off), deform_bwd_lists.h (prep, tile / row lists), deform_bwd32.h / _bwd_ws.h (D2), deform_wgrad.h (D3), deform_plane_grad.h (D4).
+// _fwd_ws.h (D1, three forms), hexplane_ops.h (the index arithmetic of the HexPlane lookup, host/device, contraction off), deform_bwd_lists.h (prep, tile / row lists), deform_bwd32.h / _bwd_ws.h (D2), deform_wgrad.h (D3), deform_plane_grad.h (D4), deform_time_grad.h (dL/dt behind a finished backward: fdgs_deform_time_grad, opt-in).
 // Knobs (development / A-B only; the table is in api.hip, the struct in common.h, the defaults are the tuned values): d1_form, d1_wgs,
 // d1_split, skip_dead, row_compact, d2_form, d4_mfma, d4_rows_kb.  Build flags: -DFDGS_PROFILE_D1 / _WS / _D2 / _D2WS / _D4 add an in-kernel
 // s_memtime phase profile of one kernel (printed once to stderr); -DFDGS_DEV_ONLY_44 builds only the (128, 32) instance.
@@ -49,6 +49,7 @@ namespace fdgs {
 #include "deform_bwd_ws.h"
 #include "deform_wgrad.h"
 #include "deform_plane_grad.h"
+#include "deform_time_grad.h"
 
 // ------------------------------------------------------------------------------------------------ host side
 static int validate_deform(const fdgs_deform_params* p) {
@@ -354,19 +355,34 @@ static int bwd_prep(hipStream_t stream, const fdgs_deform_params* p, const fdgs_
     return FDGS_OK;
 }
 
-// tiles with a non-zero gradient row -> lists (`splat`: the plane-gradient kernel the chunk list is built for; Gc = its Gaussians per chunk).
-// Leaves s.rows / s.G on the row list and the compact copy of G when the row form runs.
-static int bwd_lists(hipStream_t stream, const fdgs_deform_grads* g, float* base, const BwdLayout& bl, bool splat, int Gc, BwdScratch& s) {
-    // packed_rows_ready = 1: rows without flags -- every tile is live and the kernel writes the flags (all ones); 3: the rows of dead tiles
-    // were never written -- skipping is not a choice then, whatever the A/B knob says
+// What the backward walks, decided on the host from (p, g, the knobs) alone: fdgs_deform_bwd builds its lists by this plan, and
+// fdgs_deform_time_grad / fdgs_deform_time_grad_dfeat, which read that call's scratch afterwards, find DFEAT by the same plan.
+//   splat    the plane-gradient kernel: the matrix-core form (default whenever one frame time is shared by all Gaussians, i.e. on the render()
+//            path; d4_mfma = 1 / 0 forces a kernel (A/B, tests), otherwise the caller's order hint decides), else the per-corner atomics
+//   Gc       Gaussians per chunk of the splat (the chunk list is built for it)
+//   skip     packed_rows_ready = 1: rows without flags -- every tile is live and the kernel writes the flags (all ones); 3: the rows of dead
+//            tiles were never written -- skipping is not a choice then, whatever the A/B knob says
+//   by_rows  ROW lists instead of tile lists: D2 / D3 / D4 walk only the rows that carry a gradient (on the bench scene 12 % of the rows, but
+//            17.5 % of the 32-row tiles and 21 % of the 128-row chunks, are live).  Needs the saved activations (fetched row by row) and the
+//            splat form of D4 (which takes its chunks from any list); the dead tiles must be skippable at all (flags present).
+struct BwdListPlan { bool splat; int Gc; int skip; bool by_rows; };
+static BwdListPlan plan_bwd_lists(const fdgs_deform_params* p, const fdgs_deform_grads* g) {
+    BwdListPlan pl;
+    pl.splat = !p->time && (g_tune.d4_mfma >= 0 ? g_tune.d4_mfma != 0 : g->spatially_ordered != 0);
+    pl.Gc = 2048 / p->C;
+    pl.skip = g->packed_rows_ready == 3 ? 1 : ((g_tune.skip_dead != 0 && g->packed_rows_ready != 1) ? 1 : 0);
+    pl.by_rows = g_tune.row_compact != 0 && pl.skip && g->saved && pl.splat;
+    return pl;
+}
+
+// tiles with a non-zero gradient row -> lists.  Leaves s.rows / s.G on the row list and the compact copy of G when the row form runs.
+static int bwd_lists(hipStream_t stream, float* base, const BwdLayout& bl, const BwdListPlan& plan, BwdScratch& s) {
+    const int Gc = plan.Gc;
+    const bool by_rows = plan.by_rows;
     CompactArgs ca{};
     ca.flags = s.tile_live; ca.live = s.live; ca.chunks = s.chunks; ca.counters = s.counters; ca.G = s.G;
     ca.ntiles = s.Npad / 32; ca.tpc = Gc / 32;
-    ca.skip = g->packed_rows_ready == 3 ? 1 : ((g_tune.skip_dead != 0 && g->packed_rows_ready != 1) ? 1 : 0);
-    // ROW lists instead of tile lists: D2 / D3 / D4 walk only the rows that carry a gradient (on the bench scene 12 % of the rows, but
-    // 17.5 % of the 32-row tiles and 21 % of the 128-row chunks, are live).  Needs the saved activations (fetched row by row) and the
-    // splat form of D4 (which takes its chunks from any list); the dead tiles must be skippable at all (flags present).
-    const bool by_rows = g_tune.row_compact != 0 && ca.skip && g->saved && splat;
+    ca.skip = plan.skip;
     if (by_rows) {
         ca.rowbase = reinterpret_cast<uint32_t*>(base + bl.rowbase); ca.rows = reinterpret_cast<uint32_t*>(base + bl.rows); ca.Gc = base + bl.Gc;
         ca.row_pad = Gc > 128 ? Gc : 128;
@@ -510,8 +526,7 @@ static int launch_plane_grad(hipStream_t stream, void (*kernel)(Args), bool rais
     return FDGS_OK;
 }
 
-// plane + coordinate gradients.  splat = the matrix-core form (default whenever one frame time is shared by all Gaussians, i.e. on the
-// render() path; d4_mfma = 1 / 0 forces a kernel (A/B, tests), otherwise the caller's order hint decides), else the per-corner atomics
+// plane + coordinate gradients.  splat: the matrix-core form, else the per-corner atomics (plan_bwd_lists)
 static int bwd_plane_grads(hipStream_t stream, const fdgs_deform_params* p, const fdgs_deform_grads* g, const BwdScratch& s, bool splat, int Gc) {
     bool any_plane = g->d_xyz != nullptr;
     PlaneGradArgs ga{};
@@ -689,19 +704,117 @@ extern "C" int fdgs_deform_bwd(void* stream_, const fdgs_deform_params* p, const
     BwdScratch s = bwd_scratch(p, base, bl);
     if (!g->packed_rows_ready && (rc = bwd_prep(stream, p, g, s))) return rc;    // (1: fdgs_raster_bwd's deformation epilogue already wrote G and the identity paths)
     if (active_heads(p) == 0) return FDGS_OK;  // no head active: the deformation is the identity
-    // plane-gradient kernel choice and its chunk size (the chunk list is built for it)
-    const bool splat = !p->time && (g_tune.d4_mfma >= 0 ? g_tune.d4_mfma != 0 : g->spatially_ordered != 0);
-    const int Gc = 2048 / p->C;      // Gaussians per chunk of the splat
-    if ((rc = bwd_lists(stream, g, base, bl, splat, Gc, s))) return rc;
+    const BwdListPlan plan = plan_bwd_lists(p, g);
+    if ((rc = bwd_lists(stream, base, bl, plan, s))) return rc;
     for (int hd = 0; hd < FDGS_NUM_HEADS; hd++)
         if (p->head_on[hd]) FDGS_REQUIRE(g->d_w1[hd] && g->d_b1[hd] && g->d_w2[hd] && g->d_b2[hd], "head gradient buffer missing");
     FDGS_REQUIRE(g->d_w0 && g->d_b0, "trunk gradient buffer missing");
     if ((rc = bwd_data(stream, p, g, s))) return rc;
     if ((rc = bwd_wgrad(stream, p, g, s))) return rc;
-    return bwd_plane_grads(stream, p, g, s, splat, Gc);
+    return bwd_plane_grads(stream, p, g, s, plan.splat, plan.Gc);
 }
 
-extern "C" int fdgs_hexplane_cells(void* stream_, const fdgs_deform_params* p, int32_t* cells, float* w1, float* dscale, float* q) {
+// ---- dL/dt behind a finished backward (deform_time_grad.h).  The three entry points find DFEAT where that fdgs_deform_bwd left it: by the
+// same plan_bwd_lists, so the two cannot disagree about which list D2 walked.
+static int time_grad_blocks(const fdgs_deform_params* p) { return (int)((npad_of(p->N) + 256 + TG_ROWS - 1) / TG_ROWS); }   // (row lists are padded by < 256 entries)
+static int validate_time_grad(const fdgs_deform_params* p, const fdgs_deform_grads* g) {
+    int rc = validate_deform(p);
+    if (rc) return rc;
+    FDGS_REQUIRE(g && g->scratch, "grads/scratch is NULL");
+    return FDGS_OK;
+}
+// the scratch of the fdgs_deform_bwd that ran on (p, g), as the kernels here read it
+static void time_grad_sources(const fdgs_deform_params* p, const fdgs_deform_grads* g, const float** DFEAT, const uint32_t** tile_live,
+                              const uint32_t** rows, const uint32_t** counters) {
+    float* base = reinterpret_cast<float*>(g->scratch);
+    const BwdLayout bl = bwd_layout(p);
+    const BwdListPlan plan = plan_bwd_lists(p, g);
+    *DFEAT = base + bl.DFEAT;
+    *tile_live = reinterpret_cast<const uint32_t*>(base + bl.flags);
+    *counters = reinterpret_cast<const uint32_t*>(base + bl.counters);
+    *rows = plan.by_rows ? reinterpret_cast<const uint32_t*>(base + bl.rows) : nullptr;
+}
+
+extern "C" int fdgs_deform_time_grad_scratch_bytes(const fdgs_deform_params* p, size_t* bytes) {
+    int rc = validate_deform(p);
+    if (rc) return rc;
+    FDGS_REQUIRE(bytes, "bytes is NULL");
+    *bytes = (size_t)time_grad_blocks(p) * sizeof(float) + 256;
+    return FDGS_OK;
+}
+
+extern "C" int fdgs_deform_time_grad(void* stream_, const fdgs_deform_params* p, const fdgs_deform_grads* g, void* scratch, float* d_time) {
+    int rc = validate_time_grad(p, g);
+    if (rc) return rc;
+    FDGS_REQUIRE(scratch, "scratch is NULL");
+    FDGS_REQUIRE(d_time || (p->time && p->N == 0), "d_time is NULL");
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t nout = p->time ? (size_t)p->N : 1;
+    if (p->N == 0 || active_heads(p) == 0) {       // (no head active: the deformation is the identity and that backward built no lists)
+        if (nout) FDGS_HIP_CHECK(hipMemsetAsync(d_time, 0, nout * sizeof(float), stream));
+        return FDGS_OK;
+    }
+    TimeGradArgs a{};
+    a.p = *p; a.sc = aabb_scale(p); a.F = p->C * p->L;
+    time_grad_sources(p, g, &a.DFEAT, &a.tile_live, &a.rows, &a.counters);
+    a.d_time = p->time ? d_time : nullptr;
+    a.partials = reinterpret_cast<float*>(scratch);
+    const int blocks = p->time ? cdiv(p->N, TG_ROWS) : time_grad_blocks(p);
+    {
+        FDGS_TIMED("deform_time_grad_partial", stream);
+        if (p->C == 16) hipLaunchKernelGGL(deform_time_grad_partial_kernel<16>, dim3(blocks), dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL(deform_time_grad_partial_kernel<32>, dim3(blocks), dim3(256), 0, stream, a);
+    }
+    FDGS_LAUNCH_CHECK("deform_time_grad_partial", 0, stream);
+    if (!p->time) {
+        { FDGS_TIMED("deform_time_grad_final", stream); hipLaunchKernelGGL(deform_time_grad_final_kernel, dim3(1), dim3(256), 0, stream, a.partials, blocks, d_time); }
+        FDGS_LAUNCH_CHECK("deform_time_grad_final", 0, stream);
+    }
+    return FDGS_OK;
+}
+
+extern "C" int fdgs_deform_time_grad_dfeat(void* stream_, const fdgs_deform_params* p, const fdgs_deform_grads* g, float* dfeat, uint8_t* live) {
+    int rc = validate_time_grad(p, g);
+    if (rc) return rc;
+    if (p->N == 0) return FDGS_OK;
+    FDGS_REQUIRE(dfeat && live, "NULL pointer");
+    hipStream_t stream = (hipStream_t)stream_;
+    TimeGradProbeArgs a{};
+    a.N = p->N; a.F = p->C * p->L; a.dfeat = dfeat; a.live = live;
+    FDGS_HIP_CHECK(hipMemsetAsync(dfeat, 0, (size_t)p->N * a.F * sizeof(float), stream));
+    FDGS_HIP_CHECK(hipMemsetAsync(live, 0, (size_t)p->N, stream));
+    if (active_heads(p) == 0) return FDGS_OK;
+    time_grad_sources(p, g, &a.DFEAT, &a.tile_live, &a.rows, &a.counters);
+    const long long threads = (long long)time_grad_blocks(p) * TG_ROWS * (a.F / 4);
+    hipLaunchKernelGGL(deform_time_grad_dfeat_kernel, dim3((unsigned)cdiv(threads, 256)), dim3(256), 0, stream, a);
+    FDGS_LAUNCH_CHECK("deform_time_grad_dfeat", 0, stream);
+    return FDGS_OK;
+}
+
+extern "C" int fdgs_deform_time_grad_host(const fdgs_deform_params* p, const float* dfeat, const uint8_t* live, double* d_time_rows,
+                                          double* d_time_sum, double* abs_rows, double* abs_sum) {
+    // (only N, C, L, res, planes, aabb, xyz and time / time_scalar are read: everything else of p may be NULL / zero)
+    int rc = validate_cells(p, p ? p->xyz : nullptr, dfeat, live, dfeat);
+    if (rc) return rc;
+    FDGS_REQUIRE(p->C == 16 || p->C == 32, "output_coordinate_dim must be 16 or 32");
+    for (int l = 0; l < p->L; l++)
+        for (int k = 0; k < 6; k++) FDGS_REQUIRE(p->planes[l][k] != nullptr, "plane pointer is NULL");
+    const AabbScale sc = aabb_scale(p);
+    const size_t F = (size_t)p->C * p->L;
+    double tot = 0.0, tot_abs = 0.0;
+    for (size_t n = 0; n < (size_t)p->N; n++) {
+        double s = 0.0, sa = 0.0;
+        if (live[n]) time_grad_row_host(*p, sc.inv2, n, dfeat + n * F, &s, &sa);       // (a dead row's dfeat is never read)
+        if (d_time_rows) d_time_rows[n] = s;
+        if (abs_rows) abs_rows[n] = sa;
+        tot += s; tot_abs += sa;
+    }
+    if (d_time_sum) *d_time_sum = tot;
+    if (abs_sum) *abs_sum = tot_abs;
+    return FDGS_OK;
+}
+
+extern "C" int fdgs_hexplane_cells(void* stream_,const fdgs_deform_params* p, int32_t* cells, float* w1, float* dscale, float* q) {
     int rc = validate_cells(p, cells, w1, dscale, q);
     if (rc) return rc;
     if (p->N == 0) return FDGS_OK;

@@ -34,7 +34,7 @@ __host__ __device__ __forceinline__ int head_row0(int hd) { return hd == 0 ? 0 :
 
 // ------------------------------------------------------------------------------------------------ HexPlane gather
 // AxisSample, axis_sample and query_coord -- the index arithmetic -- live in hexplane_ops.h (contraction off, shared with the host twin)
-__device__ __forceinline__ void plane_axes(int k, int& a, int& b) {
+__host__ __device__ __forceinline__ void plane_axes(int k, int& a, int& b) {
     // pairs (0,1),(0,2),(0,3),(1,2),(1,3),(2,3): a indexes the plane's width, b its height
     a = k < 3 ? 0 : (k < 5 ? 1 : 2);
     b = k < 3 ? k + 1 : (k < 5 ? k - 1 : 3);

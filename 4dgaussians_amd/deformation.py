@@ -215,12 +215,19 @@ def deform(net, xyz, scales, rotations, opacity, shs=None, shs_dc=None, shs_rest
     """Runs the fused deformation.  Either `shs` ([N,16,3]) or the pair (shs_dc [N,1,3], shs_rest [N,15,3]) is given
     (the pair skips the torch.cat of GaussianModel.get_features, scene/gaussian_model.py:121-124).  `time` is a python
     float (one frame time for all Gaussians, as render() uses it) or a [N,1] tensor.
+    A `time` tensor that requires grad receives its gradient (opt-in; fdgs_deform_time_grad behind the backward): a [N,1] tensor the
+    per-Gaussian one, a 0-dim or [1] tensor -- one frame time, the scalar path with its plane-gradient kernels -- the sum over the rows, in
+    the tensor's shape.  The kernels take the frame time by value, so such a scalar tensor is read on the host once per forward (one
+    `.item()`, a stream synchronisation, on this opt-in path only).  A float, or a tensor that does not require grad, runs the calls it always ran.
     Returns (means3D, scales, rotations, opacity, shs [N,16,3]); with activate=True scales/rotations/opacity have had
     exp / normalize / sigmoid applied (gaussian_renderer/__init__.py:97-99).  `ordered`: the rows are spatial neighbours (None: measured
     once per position tensor, see spatial_order_hint) -- selects the plane-gradient kernel, never the result."""
     planes, mlp = _collect(net)
     dn = net.deformation_net
     cfg = _forward_cfg(dn, xyz, activate, ordered)
+    if time_wants_grad(time):
+        sh = (shs, None) if shs is not None else (shs_dc, shs_rest)
+        return _DeformTimeFunction.apply(cfg, xyz, scales, rotations, opacity, *sh, time, dn.grid.aabb, *planes, *mlp)
     if isinstance(time, torch.Tensor):
         t_tensor, t_scalar = time, 0.0
     else:
@@ -633,6 +640,68 @@ def backward_run(st, b):
     check(_lib.lib().fdgs_deform_bwd(stream_ptr(), st.p, b.g))
     note_live_tiles(st, b)
     return gradient_tuple(st, b)
+
+
+def time_wants_grad(time):
+    """A time that asks for its gradient: a tensor that requires grad, while a graph is being recorded."""
+    return isinstance(time, torch.Tensor) and time.requires_grad and torch.is_grad_enabled()
+
+
+def time_is_scalar(time):
+    """One frame time for all Gaussians: a 0-dim or [1] tensor (a [N,1] tensor, N = 1 included, is per-Gaussian)."""
+    return time.dim() < 2 and time.numel() == 1
+
+
+def time_gradient(st, b):
+    """dL/dt of the deformation whose fdgs_deform_bwd has just been queued on (st.p, b.g), on this stream: a [N] tensor where the forward had
+    per-Gaussian times, [1] (the sum over the rows) where it had one frame time."""
+    L = _lib.lib()
+    xyz, t_tensor = st.keep[0][0], st.keep[0][6]
+    nbytes = _lib.c_size_t()
+    check(L.fdgs_deform_time_grad_scratch_bytes(st.p, nbytes))
+    scratch = torch.empty(max(nbytes.value, 4), dtype=torch.uint8, device=xyz.device)
+    out = torch.empty(xyz.shape[0] if t_tensor is not None else 1, dtype=torch.float32, device=xyz.device)
+    check(L.fdgs_deform_time_grad(stream_ptr(), st.p, b.g, ptr(scratch), ptr(out)))
+    return out
+
+
+def time_gradient_like(d_time, like):
+    """The kernels' float32 [N] / [1] result as the gradient of the time tensor `like` describes (time_like)."""
+    return d_time.reshape(like[0]).to(dtype=like[1], device=like[2])
+
+
+def time_like(time):
+    return tuple(time.shape), time.dtype, time.device
+
+
+class _DeformTimeFunction(torch.autograd.Function):
+    """_DeformFunction for a time that asks for its gradient: the time tensor is an input, fdgs_deform_time_grad runs behind the same
+    fdgs_deform_bwd.  A sibling, so that every other call runs the node and the C calls it always ran."""
+
+    @staticmethod
+    def forward(ctx, cfg, xyz, scales, rotations, opacity, sh_a, sh_b, time, aabb, *rest):
+        if time_is_scalar(time):
+            t_tensor, t_scalar = None, float(time.detach().item())      # (the kernels take the frame time by value: one host read per forward)
+        else:
+            t_tensor, t_scalar = time, 0.0
+        st = forward_impl(cfg, t_scalar, xyz, scales, rotations, opacity, sh_a, sh_b, t_tensor, aabb, rest, True)
+        ctx.st, ctx.time_like = st, time_like(time)
+        ctx.save_for_backward(st.o_sc, st.o_rot, st.o_op)       # (see _DeformFunction.forward: no reference cycle through ctx)
+        outs = (st.o_xyz, st.o_sc, st.o_rot, st.o_op, st.o_sh)
+        st.o_xyz = st.o_sc = st.o_rot = st.o_op = st.o_sh = None
+        ctx.set_materialize_grads(False)
+        return outs
+
+    @staticmethod
+    def backward(ctx, g_xyz, g_sc, g_rot, g_op, g_sh):
+        st = ctx.st
+        o_sc, o_rot, o_op = ctx.saved_tensors
+        b = backward_prepare(st, o_sc, o_rot, o_op)
+        gx, gs, gr, go, gsh = map(_lib.f32, (g_xyz, g_sc, g_rot, g_op, g_sh))
+        g = b.g
+        g.g_xyz, g.g_scales, g.g_rotations, g.g_opacity, g.g_shs = ptr(gx), ptr(gs), ptr(gr), ptr(go), ptr(gsh)
+        grads = backward_run(st, b)
+        return (None,) + grads[:6] + (time_gradient_like(time_gradient(st, b), ctx.time_like),) + grads[7:]
 
 
 class _DeformFunction(torch.autograd.Function):

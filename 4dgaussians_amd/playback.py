@@ -178,7 +178,10 @@ def _render_state(who, frame_at, sh_degree, device, to_stored, to_model, viewpoi
                   cam_type, rgb8):
     """The body of Baked.render, SparseBaked.render and Composite.render: the rasterizer on the BakedFrame `frame_at(frame time)`.
     `to_stored` / `to_model` (None: the rows are stored in the model's order) take `override_color` to the stored row order and bring
-    `radii` back."""
+    `radii` back.
+    The camera's time is taken as a number, here and in every other playback render* method (render_motion, render_pick, render_contrib,
+    render_features): a baked state has no deformation to differentiate, so a time tensor that requires grad gets its gradient from
+    fdgs.render of the live model (fdgs.camera.TimeDelta), not from a playback frame."""
     if pipe.compute_cov3D_python or pipe.convert_SHs_python:
         raise NotImplementedError(f"{who}: pipe.compute_cov3D_python / pipe.convert_SHs_python need the live model; use fdgs.render")
     with torch.no_grad():
@@ -623,7 +626,8 @@ class Baked:
         with the deformation replaced by the baked state at the camera's time: the same raster settings (the PanopticSports dict camera
         included), the same result dict -- "viewspace_points" is None (nothing here takes a gradient), "radii" / "visibility_filter" are in
         the model's row order.  interp: what a time between two baked timestamps gets ("linear" | "nearest").  rgb8 = "trunc" | "round" adds
-        "rgb8", the uint8 [H,W,3] image of to_rgb8.  The pipe's python SH / covariance paths are not available from a baked state."""
+        "rgb8", the uint8 [H,W,3] image of to_rgb8.  The pipe's python SH / covariance paths are not available from a baked state.
+        The camera's time is taken as a number (no gradient to a time tensor: that is fdgs.render's, on the live model)."""
         return _render_state("Baked.render", lambda t: self.state_at(t, interp)[0], self.active_sh_degree, self.device, *self._maps,
                              viewpoint_camera, pipe, bg_color, scaling_modifier, override_color, cam_type, rgb8)
 

@@ -62,16 +62,21 @@ def _fine_stage(pc, lead=()):
     return cfg, perm, ins, (dn.grid.aabb, *planes, *mlp)
 
 
+def _time_value(t):
+    """The frame time as the number the kernels take by value (a tensor: one host read)."""
+    return float(t.detach()) if isinstance(t, torch.Tensor) else float(t)
+
+
 def _frame_settings(camera, cam_type, bg_color, scaling_modifier, sh_degree, device, pipe):
     """(GaussianRasterizationSettings, frame time) of one camera, as gaussian_renderer/__init__.py:31-58 builds them: a "PanopticSports"
     camera is a dict that brings its settings along."""
     if cam_type == "PanopticSports":
-        return camera["camera"], float(camera["time"])
+        return camera["camera"], _time_value(camera["time"])
     return GaussianRasterizationSettings(
         image_height=int(camera.image_height), image_width=int(camera.image_width), tanfovx=math.tan(camera.FoVx * 0.5),
         tanfovy=math.tan(camera.FoVy * 0.5), bg=bg_color, scale_modifier=scaling_modifier,
         viewmatrix=_dev(camera.world_view_transform, device), projmatrix=_dev(camera.full_proj_transform, device),
-        sh_degree=sh_degree, campos=_dev(camera.camera_center, device), prefiltered=False, debug=pipe.debug), float(camera.time)
+        sh_degree=sh_degree, campos=_dev(camera.camera_center, device), prefiltered=False, debug=pipe.debug), _time_value(camera.time)
 
 
 def _tile_flags():
@@ -96,7 +101,7 @@ def _fill_epilogue(st, b, assign):
     return epi
 
 
-def _fused_backward(states, saved, grad_colors, grad_depths, camera=None, grad_alphas=None, **prepare):
+def _fused_backward(states, saved, grad_colors, grad_depths, camera=None, grad_alphas=None, time=None, **prepare):
     """The backward of the fused fine stage for the views of one autograd node: states = [(deformation state, raster state)], saved = their
     (o_sc, o_rot, o_op) in a row, grad_colors / grad_depths / grad_alphas = the per-view image gradients (or None; alpha: frames rendered
     with it), `prepare` goes to backward_prepare.
@@ -104,7 +109,8 @@ def _fused_backward(states, saved, grad_colors, grad_depths, camera=None, grad_a
     rasterizer backward, whose epilogue writes into the ONE gradient arena (the first processed view assigns the identity paths, later ones
     accumulate), then that view's deformation backward -- same output pointers and scratch (stream-ordered reuse), its own saved activations.
     `camera`: a list that receives, per processed view, the 48 floats of fdgs_camera_grad, run behind that view's fdgs_raster_bwd on its
-    accumulator (frames whose camera asks for a gradient: _FusedRenderCameraFunction)."""
+    accumulator (frames whose camera asks for a gradient: _FusedRenderCameraFunction).  `time`: a list that receives, per processed view, the
+    [1] tensor of fdgs_deform_time_grad, run behind that view's fdgs_deform_bwd (frames whose time asks for one: _FusedRenderTimeFunction)."""
     L, stream = _lib.lib(), _lib.stream_ptr()
     st0 = states[0][0]
     b = _deformation.backward_prepare(st0, saved[0], saved[1], saved[2], identity_assigned=EPILOGUE_ASSIGN, **prepare)
@@ -127,6 +133,8 @@ def _fused_backward(states, saved, grad_colors, grad_depths, camera=None, grad_a
         b.g.packed_rows_ready = epi.tile_flags + 1
         _lib.check(L.fdgs_deform_bwd(stream, st.p, b.g))
         _deformation.note_live_tiles(st, b)
+        if time is not None:
+            time.append(_deformation.time_gradient(st, b))
         keep.append((gc, gd, ga, acc, epi))      # (what the queued launches read lives until the last of them is queued)
     return g_means2D, _deformation.gradient_tuple(st0, b)      # ([d means2D per view], the arena's views in _DeformFunction's input order)
 
@@ -199,6 +207,41 @@ class _FusedRenderCameraFunction(torch.autograd.Function):
         return (None, None, None, *_rasterizer.split_camera_gradients(cam[0], *ctx.cam), *g_means2D) + grads[:6] + grads[7:]
 
 
+class _FusedRenderTimeFunction(torch.autograd.Function):
+    """_FusedRenderFunction for a frame whose time asks for a gradient (a scalar tensor that requires grad: fdgs.camera.TimeDelta, tracking
+    a time against a frozen model): the time is an input and gets the [1] result of fdgs_deform_time_grad, run behind the same
+    fdgs_deform_bwd; viewmatrix, projmatrix and campos are inputs too and get fdgs_camera_grad's where one of them asks (joint pose and
+    time).  `t_scalar` is the time's value, read on the host by the caller.  A sibling, so that every other frame runs the node and the C
+    calls it always ran."""
+
+    @staticmethod
+    def forward(ctx, cfg, t_scalar, raster_settings, time, viewmatrix, projmatrix, campos, means2D, xyz, scales, rotations, opacity, sh_a, sh_b,
+                aabb, *rest):
+        st = _deformation.forward_impl(cfg, t_scalar, xyz, scales, rotations, opacity, sh_a, sh_b, None, aabb, rest, True)
+        color, radii, depth, *alpha, rstate = _rasterizer.rasterize_forward(raster_settings, st.o_xyz, st.o_sh, None, st.o_op, st.o_sc, st.o_rot, None,
+                                                                            expect_backward=True, **_alpha_kw(cfg))
+        ctx.st, ctx.rstate, ctx.cam = st, rstate, (viewmatrix, projmatrix, campos)
+        ctx.time_like, ctx.want_cam = _deformation.time_like(time), any(ctx.needs_input_grad[4:7])
+        ctx.save_for_backward(st.o_sc, st.o_rot, st.o_op)
+        st.o_xyz = st.o_sc = st.o_rot = st.o_op = st.o_sh = None
+        vis = rstate.visibility
+        ctx.mark_non_differentiable(radii, vis)
+        ctx.set_materialize_grads(False)
+        return (color, radii, depth, vis, *alpha)
+
+    @staticmethod
+    def backward(ctx, grad_color, grad_radii, grad_depth, grad_vis=None, grad_alpha=None):
+        st = ctx.st
+        if grad_color is None and grad_depth is None and grad_alpha is None:
+            return (None,) * (15 + len(st.plane_shapes) + len(st.keep[0][8]))
+        cam, tim = ([] if ctx.want_cam else None), []
+        g_means2D, grads = _fused_backward([(st, ctx.rstate)], ctx.saved_tensors, None if grad_color is None else (grad_color,),
+                                           None if grad_depth is None else (grad_depth,), camera=cam, zero_by_epilogue=EPILOGUE_ASSIGN,
+                                           grad_alphas=None if grad_alpha is None else (grad_alpha,), time=tim)
+        d_cam = _rasterizer.split_camera_gradients(cam[0], *ctx.cam) if cam else (None, None, None)
+        return (None, None, None, _deformation.time_gradient_like(tim[0], ctx.time_like), *d_cam, *g_means2D) + grads[:6] + grads[7:]
+
+
 class _FusedRenderViewsFunction(torch.autograd.Function):
     """The `batch_size` views of one optimizer step (train.py:180-201) behind ONE autograd node: every view's backward accumulates into
     the SAME gradient arena (first view: the epilogue assigns the per-Gaussian identity paths, later views accumulate), so a step pays
@@ -245,7 +288,8 @@ class _FusedRenderViewsFunction(torch.autograd.Function):
 def render_views(viewpoint_cameras, pc, pipe, bg_color, scaling_modifier=1.0, stage="fine", cam_type=None):
     """The views of one optimizer step rendered behind one autograd node: `[render(cam, ...) for cam in viewpoint_cameras]` of the
     reference's batch loop (train.py:180-198) with the same per-view result dicts, but one gradient arena for the whole step (see
-    _FusedRenderViewsFunction).  Falls back to per-view render() wherever the fused fine stage does not apply."""
+    _FusedRenderViewsFunction).  Falls back to per-view render() wherever the fused fine stage does not apply.
+    The views' times are taken as numbers: a time tensor that requires grad gets its gradient from render(), not from here."""
     cams = list(viewpoint_cameras)
     fusable = (FUSED_BACKWARD and "fine" in stage and isinstance(pc._deformation, _deformation.deform_network)
                and not pipe.compute_cov3D_python and not pipe.convert_SHs_python and len(cams) > 0)
@@ -297,7 +341,16 @@ def _dev(t, device):
     return t if t.device == device else t.to(device, non_blocking=True)
 
 
+def _time_leaf(camera, cam_type):
+    """The camera's time where it asks for a gradient -- a one-element tensor that requires grad while a graph is recorded -- else None."""
+    t = camera["time"] if cam_type == "PanopticSports" else camera.time
+    return t if _deformation.time_wants_grad(t) and t.numel() == 1 else None
+
+
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, stage="fine", cam_type=None):
+    """`viewpoint_camera.time` is a number or -- opt-in -- a one-element tensor that requires grad (fdgs.camera.TimeDelta): the fine stage
+    then also returns dL/dt into it (fdgs_deform_time_grad, reduced in HIP), the coarse stage, which does not read the time, a zero.  The
+    kernels take the time by value: such a tensor is read on the host once per frame (one `.item()`, on this opt-in path only)."""
     means3D = pc.get_xyz
     device = means3D.device
     # gradient sink for the screen-space means (train.py:223-225 reads .grad of this tensor).  A LEAF of zeros: the reference's
@@ -306,13 +359,18 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     screenspace_points = _zero_leaf(means3D)
     raster_settings, frame_time = _frame_settings(viewpoint_camera, cam_type, bg_color, scaling_modifier, pc.active_sh_degree, device, pipe)
     want_alpha = _wants_alpha(pipe)          # opt-in: "alpha" [1,H,W], the accumulated opacity, joins the result (differentiable)
+    time_leaf = _time_leaf(viewpoint_camera, cam_type)      # opt-in: the frame time as something to fit (None: every frame there was before)
     if ("fine" in stage and "coarse" not in stage and FUSED_BACKWARD and override_color is None and not pipe.compute_cov3D_python
             and not pipe.convert_SHs_python and isinstance(pc._deformation, _deformation.deform_network)):
         # deformation + rasterizer as one autograd node (see _FusedRenderFunction)
         cfg, perm, ins, net_ins = _fine_stage(pc, (screenspace_points,) if torch.is_grad_enabled() else ())
         if want_alpha:
             cfg["alpha"] = True
-        if cfg["grad"] and _rasterizer.camera_wants_grad(raster_settings):
+        if cfg["grad"] and time_leaf is not None:
+            rs = raster_settings
+            rendered_image, radii, depth, vis, *alpha = _FusedRenderTimeFunction.apply(cfg, frame_time, rs, time_leaf, rs.viewmatrix, rs.projmatrix,
+                                                                                       rs.campos, *ins, *net_ins)
+        elif cfg["grad"] and _rasterizer.camera_wants_grad(raster_settings):
             rs = raster_settings
             rendered_image, radii, depth, vis, *alpha = _FusedRenderCameraFunction.apply(cfg, frame_time, rs, rs.viewmatrix, rs.projmatrix, rs.campos,
                                                                                          *ins, *net_ins)
@@ -351,9 +409,9 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         if fused:
             means3D_final, scales_final, rotations_final, opacity_final, shs_final = _deformation.deform(
                 pc._deformation, means3D, scales, rotations, opacity, shs_dc=pc._features_dc, shs_rest=pc._features_rest,
-                time=frame_time, activate=True)
+                time=frame_time if time_leaf is None else time_leaf.reshape(()), activate=True)
         else:
-            time = torch.tensor(frame_time).to(device).repeat(means3D.shape[0], 1)
+            time = (torch.tensor(frame_time) if time_leaf is None else time_leaf.reshape(1, 1)).to(device).repeat(means3D.shape[0], 1)
             means3D_final, scales_final, rotations_final, opacity_final, shs_final = pc._deformation(
                 means3D, scales, rotations, opacity, pc.get_features, time)
             scales_final = None if scales_final is None else pc.scaling_activation(scales_final)
@@ -382,6 +440,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     rendered_image, radii, depth, *alpha = rasterizer(
         means3D=means3D_final, means2D=means2D, shs=shs_final, colors_precomp=colors_precomp, opacities=opacity_final,
         scales=scales_final, rotations=rotations_final, cov3D_precomp=cov3D_precomp)
+    if time_leaf is not None and "coarse" in stage:      # (the coarse stage does not read the time: its gradient is a zero, not a missing one)
+        rendered_image = rendered_image + (time_leaf * 0).sum().to(device=rendered_image.device, dtype=rendered_image.dtype)
     res = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
            "radii": radii, "depth": depth}
     if alpha:

@@ -401,6 +401,29 @@ int fdgs_deform_bwd_live_tiles(void* stream, const fdgs_deform_params* p, const 
 int fdgs_hexplane_cells(void* stream, const fdgs_deform_params* p, int32_t* cells, float* w1, float* dscale, float* q);
 int fdgs_hexplane_cells_host(const fdgs_deform_params* p, int32_t* cells, float* w1, float* dscale, float* q);
 
+/* The gradient of the time (additions to ABI 6; no existing signature or struct changed).  The time reaches the deformation only through the
+ * fourth HexPlane coordinate, so dL/dt is the coordinate gradient of the three time planes:
+ *   dt_n = sum_lvl sum_c dfeat[n][lvl C + c] * sum_{k in (x,t),(y,t),(z,t)} (prod_{k' != k} v_k'[c]) * dscale_t * sum_x w_x (P_k[t1][x][c] - P_k[t0][x][c])
+ * with dfeat = dL/d(HexPlane features), which fdgs_deform_bwd forms and leaves in its scratch.  dscale_t = 0 where the border clamp is
+ * active: a time at or beyond the last time row has a gradient of exactly 0.  Opt-in: a frame that does not call these runs what it ran.
+ *   fdgs_deform_time_grad   is called AFTER fdgs_deform_bwd(stream, p, g), with the same p, g (and the same tuning knobs) on the same stream,
+ *       and reads that call's scratch.  d_time is float [N] when p->time is set (the kernel stores every row, 0 for rows without a gradient:
+ *       no fill by the caller), float [1] otherwise: the sum over the rows, reduced in a fixed order without float atomics (per workgroup in
+ *       float through LDS, the workgroups' partials by one workgroup in double) -- for a given scratch the same bits on every run.
+ *       `scratch`: fdgs_deform_time_grad_scratch_bytes(p) bytes.  N == 0, no active head or no row with a gradient give zeros.
+ *       Two launches (one with p->time), none of them on the default frame path.
+ *   fdgs_deform_time_grad_dfeat   a probe (tests): dfeat of that backward in Gaussian order, float [N][C*L] (0 for dead rows), and one
+ *       byte per row, 1 = the backward computed the row's dfeat.
+ *   fdgs_deform_time_grad_host   the host twin over host arrays (of p only N, C, L, res, planes, aabb, xyz, time / time_scalar are read): the
+ *       same index arithmetic (csrc/hexplane_ops.h), every sum in double.  Rows with live[n] == 0 are not read and give 0.  d_time_rows /
+ *       abs_rows double [N], d_time_sum / abs_sum double [1]: the sums of the addends and of their absolute values, per row and over all
+ *       rows; any of the four may be NULL. */
+int fdgs_deform_time_grad_scratch_bytes(const fdgs_deform_params* p, size_t* bytes);
+int fdgs_deform_time_grad(void* stream, const fdgs_deform_params* p, const fdgs_deform_grads* g, void* scratch, float* d_time);
+int fdgs_deform_time_grad_dfeat(void* stream, const fdgs_deform_params* p, const fdgs_deform_grads* g, float* dfeat, uint8_t* live);
+int fdgs_deform_time_grad_host(const fdgs_deform_params* p, const float* dfeat, const uint8_t* live, double* d_time_rows, double* d_time_sum,
+                               double* abs_rows, double* abs_sum);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Loss-side helper for the frame-parallel driver: accumulates [sum|a-b|, sum (a-b)^2, n] into acc[3] (device,
  * caller zero-fills) and optionally writes dL/da = sign(a-b)*scale.  (utils/loss_utils.py:20-21, image_utils.py:17-38)
