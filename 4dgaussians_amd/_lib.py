@@ -141,6 +141,16 @@ SYMBOLS = {
     "fdgs_raster_fwd_capacity_alpha": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p,
                                                c_void_p, c_void_p]),
     "fdgs_raster_bwd_alpha": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_uint32, POINTER(RasterGrads), c_void_p]),
+    # ... antialiased: the projection compensates the opacity for the dilation (opacity * h); forward, backward and camera gradient of one
+    # frame take the same case.  fwd_capacity_aa / raster_bwd_aa carry the optional alpha image / its gradient of the alpha forms
+    "fdgs_preprocess_fwd_aa": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p]),
+    "fdgs_raster_fwd_capacity_aa": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p]),
+    "fdgs_raster_bwd_aa": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_uint32, POINTER(RasterGrads), c_void_p]),
+    "fdgs_camera_grad_aa": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fdgs_preprocess_host_aa": (c_int, [POINTER(RasterParams)] + [c_void_p] * 10),
+    "fdgs_preprocess_bwd_host_aa": (c_int, [POINTER(RasterParams)] + [c_void_p] * 15),
+    "fdgs_camera_grad_host_aa": (c_int, [POINTER(RasterParams)] + [c_void_p] * 9),
     "fdgs_mark_visible": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdgs_preprocess_host": (c_int, [POINTER(RasterParams)] + [c_void_p] * 9),
     "fdgs_preprocess_bwd_host": (c_int, [POINTER(RasterParams)] + [c_void_p] * 13),

@@ -819,9 +819,11 @@ extern "C" int fdgs_bin_sort(void* stream_, const fdgs_raster_params* p, void* g
     return bin_sort_impl(stream_, p, geom, binning, img, R, false);
 }
 
-// fdgs_raster_fwd_capacity (out_alpha == nullptr) and fdgs_raster_fwd_capacity_alpha
+// fdgs_raster_fwd_capacity (out_alpha == nullptr), fdgs_raster_fwd_capacity_alpha and fdgs_raster_fwd_capacity_aa (antialiasing: only the
+// projection differs -- everything behind it reads recB and the cull mask the projection wrote, never the opacity input)
 static int raster_fwd_capacity_impl(void* stream, const fdgs_raster_params* p, void* geom, void* binning, void* img, uint32_t capacity,
-                                    uint32_t* num_rendered_host, int32_t* radii, float* out_color, float* out_depth, float* out_alpha) {
+                                    uint32_t* num_rendered_host, int32_t* radii, float* out_color, float* out_depth, float* out_alpha,
+                                    bool antialiasing = false) {
     FDGS_REQUIRE(capacity > 0 && binning, "capacity mode needs a binning buffer of fdgs_binning_bytes(capacity) bytes, capacity > 0");
     // the count's way to the host: a store by the LAST workgroup of the projection kernel into the (pinned, device-visible) word -- it is in
     // host memory while the depth sort is still running; a copy node if the word is not device-visible (a 4-byte copy costs the stream
@@ -830,7 +832,7 @@ static int raster_fwd_capacity_impl(void* stream, const fdgs_raster_params* p, v
     const bool zero_copy = p && p->P > 0 && hipHostGetDevicePointer(&dp, num_rendered_host, 0) == hipSuccess && dp != nullptr;
     if (!zero_copy) (void)hipGetLastError();
     const bool counted = p && p->P > 0 && p->W > 0 && p->H > 0 && counts_in_projection(img_layout(p->W, p->H));
-    int rc = fdgs_preprocess_fwd_impl(stream, p, geom, radii, zero_copy ? reinterpret_cast<uint32_t*>(dp) : nullptr, counted);
+    int rc = fdgs_preprocess_fwd_impl(stream, p, geom, radii, zero_copy ? reinterpret_cast<uint32_t*>(dp) : nullptr, counted, antialiasing);
     if (rc) return rc;
     rc = bin_prepare_impl(stream, p, geom, num_rendered_host, false, zero_copy);
     if (rc) return rc;
@@ -848,6 +850,11 @@ extern "C" int fdgs_raster_fwd_capacity(void* stream, const fdgs_raster_params* 
 extern "C" int fdgs_raster_fwd_capacity_alpha(void* stream, const fdgs_raster_params* p, void* geom, void* binning, void* img, uint32_t capacity,
                                               uint32_t* num_rendered_host, int32_t* radii, float* out_color, float* out_depth, float* out_alpha) {
     return raster_fwd_capacity_impl(stream, p, geom, binning, img, capacity, num_rendered_host, radii, out_color, out_depth, out_alpha);
+}
+
+extern "C" int fdgs_raster_fwd_capacity_aa(void* stream, const fdgs_raster_params* p, void* geom, void* binning, void* img, uint32_t capacity,
+                                           uint32_t* num_rendered_host, int32_t* radii, float* out_color, float* out_depth, float* out_alpha) {
+    return raster_fwd_capacity_impl(stream, p, geom, binning, img, capacity, num_rendered_host, radii, out_color, out_depth, out_alpha, true);
 }
 
 // Host side of the verified capacity path: wait until the pair count of a frame queued by fdgs_raster_fwd_capacity has reached its pinned

@@ -28,6 +28,7 @@ namespace fdgs {
 #define FDGS_ALPHA_MIN (1.0f / 255.0f)
 #define FDGS_T_STOP 0.0001f
 #define FDGS_DENOM_EPS 0.0000001f
+#define FDGS_AA_FLOOR 0.000025f
 
 #define FDGS_SH_C0 0.28209479177387814f
 #define FDGS_SH_C1 0.4886025119029199f
@@ -99,16 +100,96 @@ FDGS_HD void ewa_M(const CamConst& c, const float* pv, float* Mx, float* tc, boo
     }
 }
 
-// cov2D (with dilation) from M and Sigma; also returns MS = M*Sigma (2x3) for the backward
-FDGS_HD void cov2d_from(const float* Mx, const float* c6, float* abc, float* MS) {
+// cov2D (with dilation) from M and Sigma; also returns MS = M*Sigma (2x3) for the backward and, where asked (antialiasing), the diagonal
+// before the dilation, AC = (A, C): the very sums the dilation is added to
+FDGS_HD void cov2d_from(const float* Mx, const float* c6, float* abc, float* MS, float* AC = nullptr) {
     const float S[9] = {c6[0], c6[1], c6[2], c6[1], c6[3], c6[4], c6[2], c6[4], c6[5]};
 #pragma unroll
     for (int r = 0; r < 2; r++)
 #pragma unroll
         for (int j = 0; j < 3; j++) MS[3 * r + j] = Mx[3 * r] * S[j] + Mx[3 * r + 1] * S[3 + j] + Mx[3 * r + 2] * S[6 + j];
-    abc[0] = MS[0] * Mx[0] + MS[1] * Mx[1] + MS[2] * Mx[2] + FDGS_DILATION;
+    const float A = MS[0] * Mx[0] + MS[1] * Mx[1] + MS[2] * Mx[2];
+    const float C = MS[3] * Mx[3] + MS[4] * Mx[4] + MS[5] * Mx[5];
+    abc[0] = A + FDGS_DILATION;
     abc[1] = MS[0] * Mx[3] + MS[1] * Mx[4] + MS[2] * Mx[5];
-    abc[2] = MS[3] * Mx[3] + MS[4] * Mx[4] + MS[5] * Mx[5] + FDGS_DILATION;
+    abc[2] = C + FDGS_DILATION;
+    if (AC) { AC[0] = A; AC[1] = C; }
+}
+
+// ---- antialiasing: opacity compensation for the dilation (the EWA normalisation of Mip-Splatting; upstream's `antialiasing`) -----------
+// The dilation spreads a splat over a larger footprint without lowering its peak; the compensation scales the opacity by the ratio of
+// the two footprints' areas, h = sqrt(max(FDGS_AA_FLOOR, r)), r = D0 / D1, D0 = A C - b^2 (before the dilation), D1 = a c - b^2 (after).
+// The floor is upstream's.  abc = (a, b, c) with the dilation, AC = (A, C) without.  aa_comp: the backward's evaluation, in float (its
+// results are held to the gradient bound); the forward's h comes from aa_ratio_f64 below.
+struct AAComp { float h, r, D0, D1; };
+FDGS_HD AAComp aa_comp(const float* abc, const float* AC) {
+    AAComp k;
+    k.D0 = AC[0] * AC[1] - abc[1] * abc[1];
+    k.D1 = abc[0] * abc[2] - abc[1] * abc[1];
+    k.r = k.D0 / k.D1;
+    k.h = sqrtf(fmaxf(FDGS_AA_FLOOR, k.r));
+    return k;
+}
+// The forward's r, evaluated in DOUBLE from the kernel's float inputs (position, scale / rotation or the covariance given, camera) and
+// rounded once.  In float, A and C arrive through a dozen roundings (view transform, J, M, Sigma, M Sigma M^T), and for a footprint below
+// the dilation h ~ sqrt(A C) / 0.3 inherits half of their sum: 4 .. 6 ulp of opacity * h against a float64 evaluation, measured on the
+// test scenes (tests/test_antialias_host.py) -- the float32 evaluation of the reference formulas is off by as much.  About 150 double
+// operations per visible Gaussian, in the antialiased instantiation only.  from_sq: Sigma is formed from s and q; else c6 is the
+// covariance the caller gave (a flag, not a NULL test: a pointer that may be NULL puts the kernel's s[] and q[] into scratch).
+FDGS_HD float aa_ratio_f64(const CamConst& c, const float* p, const float* c6, const float* s, const float* q, bool from_sq) {
+    double S[9];
+    if (from_sq) {
+        const double r = q[0], x = q[1], y = q[2], z = q[3];
+        const double R[9] = {1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - r * z), 2.0 * (x * z + r * y),
+                             2.0 * (x * y + r * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - r * x),
+                             2.0 * (x * z - r * y), 2.0 * (y * z + r * x), 1.0 - 2.0 * (x * x + y * y)};
+        double L[9];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) L[3 * i + k] = R[3 * i + k] * ((double)c.scale_mod * (double)s[k]);
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) S[3 * i + j] = L[3 * i] * L[3 * j] + L[3 * i + 1] * L[3 * j + 1] + L[3 * i + 2] * L[3 * j + 2];
+    } else {
+        S[0] = c6[0]; S[1] = c6[1]; S[2] = c6[2]; S[3] = c6[1]; S[4] = c6[3]; S[5] = c6[4]; S[6] = c6[2]; S[7] = c6[4]; S[8] = c6[5];
+    }
+    const float* v = c.view;
+    const double px = p[0], py = p[1], pz = p[2];
+    const double tx0 = v[0] * px + v[4] * py + v[8] * pz + v[12], ty0 = v[1] * px + v[5] * py + v[9] * pz + v[13];
+    const double tz = v[2] * px + v[6] * py + v[10] * pz + v[14];
+    const double limx = 1.3 * (double)c.tanfovx, limy = 1.3 * (double)c.tanfovy;
+    const double tx = fmin(limx, fmax(-limx, tx0 / tz)) * tz, ty = fmin(limy, fmax(-limy, ty0 / tz)) * tz;
+    const double fx = (double)c.W / (2.0 * (double)c.tanfovx), fy = (double)c.H / (2.0 * (double)c.tanfovy);
+    const double J00 = fx / tz, J02 = -(fx * tx) / (tz * tz), J11 = fy / tz, J12 = -(fy * ty) / (tz * tz);
+    double M[6];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        M[j] = J00 * v[4 * j + 0] + J02 * v[4 * j + 2];
+        M[3 + j] = J11 * v[4 * j + 1] + J12 * v[4 * j + 2];
+    }
+    double MS[6];
+#pragma unroll
+    for (int r = 0; r < 2; r++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) MS[3 * r + j] = M[3 * r] * S[j] + M[3 * r + 1] * S[3 + j] + M[3 * r + 2] * S[6 + j];
+    const double A = MS[0] * M[0] + MS[1] * M[1] + MS[2] * M[2], b = MS[0] * M[3] + MS[1] * M[4] + MS[2] * M[5];
+    const double C = MS[3] * M[3] + MS[4] * M[4] + MS[5] * M[5];
+    const double a = A + (double)FDGS_DILATION, cc = C + (double)FDGS_DILATION;      // (the dilation the float path adds: the float 0.3)
+    return (float)((A * C - b * b) / (a * cc - b * b));
+}
+
+// dL/dr -> (da, db, dc) += of the dilated covariance (d a = d A, d c = d C; db the full derivative with respect to b).  Plain divisions:
+// the 1e-7 regulariser of project_bwd_view belongs to the conic's inverse only.  g_op = dL/d(opacity * h) * opacity.  At or below the
+// floor (and for a NaN r) the path gives exactly zero; a zero g_op adds nothing, not even a signed zero.
+FDGS_HD void aa_bwd(const AAComp& k, const float* abc, const float* AC, float g_op, float* da, float* db, float* dc) {
+    if (g_op == 0.0f || !(k.r > FDGS_AA_FLOOR)) return;
+    const float dr = g_op / (2.0f * k.h);
+    const float D1sq = k.D1 * k.D1;
+    *da += dr * ((AC[1] * k.D1 - k.D0 * abc[2]) / D1sq);
+    *dc += dr * ((AC[0] * k.D1 - k.D0 * abc[0]) / D1sq);
+    *db += dr * ((2.0f * abc[1] * (k.D0 - k.D1)) / D1sq);
 }
 
 FDGS_HD float ndc2pix(float v, int S) { return ((v + 1.0f) * (float)S - 1.0f) * 0.5f; }
@@ -117,10 +198,15 @@ struct GeoOut {
     float depth, px, py, conic[3];
     int radius, tiles;
     uint32_t rect_min, rect_max;  // x | y<<16
+    float aa;                     // project_gaussian<true> only: the opacity compensation h (aa_comp)
 };
 
-// Appendix B.1 (everything except colour). Returns false when the Gaussian is culled.
-FDGS_HD bool project_gaussian(const CamConst& c, const float* p, const float* c6, GeoOut* o) {
+// Appendix B.1 (everything except colour). Returns false when the Gaussian is culled.  AA: also the opacity compensation of the dilation,
+// o->aa (from_sq: c6 was formed from the scale s and the rotation q; else it is the covariance given: aa_ratio_f64); nothing else
+// changes -- conic, radius, rect, depth and the det == 0 cull use the dilated covariance either way.
+template <bool AA = false>
+FDGS_HD bool project_gaussian(const CamConst& c, const float* p, const float* c6, GeoOut* o, const float* s = nullptr, const float* q = nullptr,
+                              bool from_sq = false) {
     float pv[3];
     view_xform(c.view, p, pv);
     if (pv[2] <= FDGS_NEAR_CULL) return false;
@@ -133,6 +219,7 @@ FDGS_HD bool project_gaussian(const CamConst& c, const float* p, const float* c6
     cov2d_from(Mx, c6, abc, MS);
     float det = abc[0] * abc[2] - abc[1] * abc[1];
     if (det == 0.0f) return false;
+    if constexpr (AA) o->aa = sqrtf(fmaxf(FDGS_AA_FLOOR, aa_ratio_f64(c, p, c6, s, q, from_sq)));
     float det_inv = 1.0f / det;
     o->conic[0] = abc[2] * det_inv; o->conic[1] = -abc[1] * det_inv; o->conic[2] = abc[0] * det_inv;
     float mid = 0.5f * (abc[0] + abc[2]);
@@ -312,14 +399,17 @@ FDGS_HD void mean2d_grad_to_ndc(float gx_pix, float gy_pix, int W, int H, float*
 // The part of project_bwd the camera's gradient shares with it (camera_terms below): conic / depth gradients -> dcov6 (written),
 // dpv = dL/d(view-space centre) = (dtx, dty, dtz) with the clamp flags and the depth term applied, dM = dL/d(J*Rv) (2x3) and
 // J = (J00, J02, J11, J12) of the clamped centre.
+// AA (a frame projected with project_gaussian<true>): g_op = dL/d(opacity * h) * opacity enters da, db, dc through aa_bwd, and from there
+// dcov6, dM and the view-space centre like the conic's share, with the same clamp conventions; *h = the compensation, for dL/dopacity.
+template <bool AA = false>
 FDGS_HD void project_bwd_view(const CamConst& c, const float* p, const float* c6, const float* dconic /*xx, xy(half), yy*/,
-                              float ddepth, float* dcov6, float* dpv, float* dM, float* J) {
+                              float ddepth, float* dcov6, float* dpv, float* dM, float* J, float g_op = 0.0f, float* h = nullptr) {
     float pv[3];
     view_xform(c.view, p, pv);
-    float Mx[6], tc[3], abc[3], MS[6];
+    float Mx[6], tc[3], abc[3], MS[6], AC[2];
     bool xc, yc;
     ewa_M(c, pv, Mx, tc, &xc, &yc);
-    cov2d_from(Mx, c6, abc, MS);
+    cov2d_from(Mx, c6, abc, MS, AA ? AC : nullptr);
     float a = abc[0], b = abc[1], cc = abc[2];
     float denom = a * cc - b * b;
     float d2i = 1.0f / (denom * denom + FDGS_DENOM_EPS);
@@ -330,6 +420,11 @@ FDGS_HD void project_bwd_view(const CamConst& c, const float* p, const float* c6
         da = d2i * (-cc * cc * kx + 2.0f * b * cc * ky + (denom - a * cc) * kz);
         dc = d2i * (-a * a * kz + 2.0f * a * b * ky + (denom - a * cc) * kx);
         db = d2i * 2.0f * (b * cc * kx - (denom + 2.0f * b * b) * ky + a * b * kz);
+    }
+    if constexpr (AA) {
+        const AAComp k = aa_comp(abc, AC);
+        *h = k.h;
+        aa_bwd(k, abc, AC, g_op, &da, &db, &dc);
     }
     // G2 = [[da, db/2],[db/2, dc]];  GM = G2*M (2x3);  dSigma_full = M^T GM;  dM = 2*GM*Sigma
     float hb = 0.5f * db;
@@ -367,10 +462,11 @@ FDGS_HD void project_bwd_view(const CamConst& c, const float* p, const float* c6
 }
 
 // conic / depth / mean2D gradients -> dmean (+=), dcov6 (written)
+template <bool AA = false>
 FDGS_HD void project_bwd(const CamConst& c, const float* p, const float* c6, const float* dconic /*xx, xy(half), yy*/,
-                         float ddepth, float g_ndc_x, float g_ndc_y, float* dmean, float* dcov6) {
+                         float ddepth, float g_ndc_x, float g_ndc_y, float* dmean, float* dcov6, float g_op = 0.0f, float* h = nullptr) {
     float dpv[3], dM[6], J[4];
-    project_bwd_view(c, p, c6, dconic, ddepth, dcov6, dpv, dM, J);
+    project_bwd_view<AA>(c, p, c6, dconic, ddepth, dcov6, dpv, dM, J, g_op, h);
     const float dtx = dpv[0], dty = dpv[1], dtz = dpv[2];
     const float* v = c.view;
     dmean[0] += v[0] * dtx + v[1] * dty + v[2] * dtz;
@@ -394,10 +490,12 @@ FDGS_HD void project_bwd(const CamConst& c, const float* p, const float* c6, con
 //   t[12 + 3*r + k]  = dL/dprojmatrix[4*r + c], c = (0, 1, 3)[k] (column 2 is exactly 0): ph_r * dhom_c, dhom the derivative of the NDC position
 //                      through mw = 1 / (w + FDGS_W_EPS) (the terms behind mul1 / mul2 of project_bwd)
 //   t[24 + k]        = dL/dcampos[k]: minus what sh_bwd adds to dmean (colour clamp mask applied there); 0 without SH (sh == NULL)
+// AA: g_op as project_bwd_view takes it; the compensation's share reaches dpv and dM there, so every term below includes it.
+template <bool AA = false>
 FDGS_HD void camera_terms(const CamConst& c, const float* p, const float* c6, const float* dconic /*xx, xy(half), yy*/, float ddepth,
-                          float g_ndc_x, float g_ndc_y, const float* sh, uint32_t clamped, const float* dL_drgb, float* t) {
-    float dcov6[6], dpv[3], dM[6], J[4];
-    project_bwd_view(c, p, c6, dconic, ddepth, dcov6, dpv, dM, J);
+                          float g_ndc_x, float g_ndc_y, const float* sh, uint32_t clamped, const float* dL_drgb, float* t, float g_op = 0.0f) {
+    float dcov6[6], dpv[3], dM[6], J[4], h_unused;
+    project_bwd_view<AA>(c, p, c6, dconic, ddepth, dcov6, dpv, dM, J, g_op, &h_unused);
     const float ph[4] = {p[0], p[1], p[2], 1.0f};
     // J = [[J00, 0, J02], [0, J11, J12]]
     const float Jc[6] = {J[0], 0.0f, J[1], 0.0f, J[2], J[3]};

@@ -54,7 +54,9 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
 
 // COUNT: the kernel also counts the pairs of every tile (a.tile_counts; the one-call frame with knob bin_count).  An instantiation of its own:
 // the staged calls and the images that keep the count launch run the kernel without the square and the mask held to its end.
-template <bool COUNT>
+// AA (the *_aa entry points): the opacity written into recB.y, and the one the cull ellipse is set up from, is opacity * h, h the
+// compensation of the dilation (gs_math.h aa_comp).  An instantiation of its own as well: the other keeps its instructions.
+template <bool COUNT, bool AA>
 __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreFwdArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     CamConst c;
@@ -64,18 +66,18 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreFwdArgs a) {
     unsigned long long my_mask[4] = {0ull, 0ull, 0ull, 0ull};           // ... and, culled, the tiles of it that can receive a contribution
     if (i < a.P) {
         float p[3] = {a.means3D[3 * (size_t)i], a.means3D[3 * (size_t)i + 1], a.means3D[3 * (size_t)i + 2]};
-        float c6[6];
+        float c6[6], s[3] = {0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
         if (a.cov3D_precomp) {
 #pragma unroll
             for (int k = 0; k < 6; k++) c6[k] = a.cov3D_precomp[6 * (size_t)i + k];
         } else {
-            float s[3] = {a.scales[3 * (size_t)i], a.scales[3 * (size_t)i + 1], a.scales[3 * (size_t)i + 2]};
+            s[0] = a.scales[3 * (size_t)i]; s[1] = a.scales[3 * (size_t)i + 1]; s[2] = a.scales[3 * (size_t)i + 2];
             const float4 qv = reinterpret_cast<const float4*>(a.rotations)[i];
-            float q[4] = {qv.x, qv.y, qv.z, qv.w};
+            q[0] = qv.x; q[1] = qv.y; q[2] = qv.z; q[3] = qv.w;
             cov3d_from_scale_rot(s, c.scale_mod, q, c6);
         }
         GeoOut g;
-        bool vis = project_gaussian(c, p, c6, &g);
+        bool vis = project_gaussian<AA>(c, p, c6, &g, s, q, a.cov3D_precomp == nullptr);
         int32_t radius = 0;
         uint32_t key = 0xFFFFFFFFu;
         if (vis) {
@@ -99,9 +101,11 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreFwdArgs a) {
                     cl = sh_to_rgb(c.D, sh, p, c.campos, rgb);
                 }
             }
+            float opacity = a.opacities[i];
+            if constexpr (AA) opacity *= g.aa;
             a.depth[i] = g.depth;
             a.recA[i] = make_float4(g.px, g.py, g.conic[0], g.conic[1]);
-            a.recB[i] = make_float4(g.conic[2], a.opacities[i], g.depth, 0.f);
+            a.recB[i] = make_float4(g.conic[2], opacity, g.depth, 0.f);
             a.recC[i] = make_float4(rgb[0], rgb[1], rgb[2], 0.f);
 #pragma unroll
             for (int k = 0; k < 6; k++) a.cov3D[6 * (size_t)i + k] = c6[k];
@@ -115,7 +119,7 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(PreFwdArgs a) {
                 const int rx0 = (int)(g.rect_min & 0xFFFFu), ry0 = (int)(g.rect_min >> 16);
                 const int rx1 = (int)(g.rect_max & 0xFFFFu), ry1 = (int)(g.rect_max >> 16), w = rx1 - rx0;
                 unsigned long long m[4] = {0ull, 0ull, 0ull, 0ull};
-                const CullEllipse E = cull_setup(g.conic, a.opacities[i]);
+                const CullEllipse E = cull_setup(g.conic, opacity);
                 uint32_t cnt = 0;
                 if (E.mode != 0) {
                     for (int ty = ry0; ty < ry1; ty++) {
@@ -226,7 +230,9 @@ __device__ __forceinline__ void wave_store_rows(float* __restrict__ out_block, c
 // EPI: instead of dL_dmeans3D / dL_dscales / dL_drot / dL_dopacity / dL_dsh the kernel writes what fdgs_deform_bwd consumes: the packed
 // pre-activation gradient rows G[Npad][64] (activation Jacobians applied) and the identity paths, block-linear like everything else
 // (this is deform_bwd_prep_kernel's job done where the values are still in registers: one kernel and 2 x 236 B per Gaussian less).
-template <bool EPI>
+// AA (the state was projected by preprocess_fwd_kernel<*, true>): the opacity sum of the accumulator line is g = dL/d(opacity * h), so
+// dL/dopacity = h * g and g * opacity enters the covariance's gradient through h (gs_math.h aa_bwd); any_grad already covers the word.
+template <bool EPI, bool AA>
 __global__ void __launch_bounds__(256) preprocess_bwd_kernel(PreBwdArgs a) {
     __shared__ __attribute__((aligned(16))) float lds_all[4 * 64 * (EPI ? 64 : 48)];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -298,7 +304,13 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(PreBwdArgs a) {
         dop = g1.y;
         drgb[0] = g1.z; drgb[1] = g1.w; drgb[2] = g2.x;
         float dconic[3] = {g0.z, g0.w, g1.x};
-        project_bwd(c, p, c6, dconic, g2.y, m2d[0], m2d[1], dmean, dcov6);
+        if constexpr (AA) {
+            float h;
+            project_bwd<true>(c, p, c6, dconic, g2.y, m2d[0], m2d[1], dmean, dcov6, g1.y * a.opacities[i], &h);
+            dop = h * g1.y;
+        } else {
+            project_bwd(c, p, c6, dconic, g2.y, m2d[0], m2d[1], dmean, dcov6);
+        }
         if (a.shs) {
             const float* sh = a.shs + (size_t)i * a.M * 3;
             sh_bwd(c.D, sh, p, c.campos, a.clamped[i], drgb, dsh, dmean);
@@ -489,8 +501,11 @@ struct CamGradArgs : FrameHead {
     const float* cov3D; const uint32_t *tiles, *clamped;
     const float* gacc;           // [P,16] as PreBwdArgs
     float* partial;              // [gridDim.x][CAM_ROW]
+    const float* opacities;      // AA: the opacities the projection received
 };
 
+// AA: as preprocess_bwd_kernel<*, true> -- the opacity sum of the line times the opacity enters camera_terms
+template <bool AA>
 __global__ void __launch_bounds__(256) camera_grad_partial_kernel(CamGradArgs a) {
     __shared__ float wsum[4][CAM_ROW];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -519,8 +534,13 @@ __global__ void __launch_bounds__(256) camera_grad_partial_kernel(CamGradArgs a)
             float m2d[2];
             mean2d_grad_to_ndc(g0.x, g0.y, a.W, a.H, m2d);
             const float dconic[3] = {g0.z, g0.w, g1.x}, drgb[3] = {g1.z, g1.w, g2.x};
-            camera_terms(c, p, c6, dconic, g2.y, m2d[0], m2d[1], a.shs ? a.shs + (size_t)i * a.M * 3 : nullptr, a.shs ? a.clamped[i] : 0u,
-                         drgb, t);
+            if constexpr (AA) {
+                camera_terms<true>(c, p, c6, dconic, g2.y, m2d[0], m2d[1], a.shs ? a.shs + (size_t)i * a.M * 3 : nullptr,
+                                   a.shs ? a.clamped[i] : 0u, drgb, t, g1.y * a.opacities[i]);
+            } else {
+                camera_terms(c, p, c6, dconic, g2.y, m2d[0], m2d[1], a.shs ? a.shs + (size_t)i * a.M * 3 : nullptr, a.shs ? a.clamped[i] : 0u,
+                             drgb, t);
+            }
         }
 #pragma unroll
         for (int k = 0; k < CAM_TERMS; k++) {
@@ -598,7 +618,14 @@ int validate_raster_params(const fdgs_raster_params* p) {
 
 using namespace fdgs;
 
-int fdgs_preprocess_fwd_impl(void* stream_, const fdgs_raster_params* p, void* geom, int32_t* radii, uint32_t* host_count_dev, bool count_tiles) {
+template <bool AA>
+static void launch_preprocess_fwd(hipStream_t stream, bool count_tiles, int P, size_t lds, const PreFwdArgs& a) {
+    void (*const kernel)(PreFwdArgs) = count_tiles ? preprocess_fwd_kernel<true, AA> : preprocess_fwd_kernel<false, AA>;
+    hipLaunchKernelGGL(kernel, dim3(cdiv(P, 256)), dim3(256), lds, stream, a);
+}
+
+int fdgs_preprocess_fwd_impl(void* stream_, const fdgs_raster_params* p, void* geom, int32_t* radii, uint32_t* host_count_dev, bool count_tiles,
+                             bool antialiasing) {
     int rc = validate_raster_params(p);
     if (rc) return rc;
     FDGS_REQUIRE(geom && (radii || p->P == 0), "geom/radii is NULL");
@@ -625,14 +652,20 @@ int fdgs_preprocess_fwd_impl(void* stream_, const fdgs_raster_params* p, void* g
         FDGS_REQUIRE(gl.tile_counts == gl.total + 256, "the tile counters follow the header");
         a.tile_counts = at<uint32_t>(geom, gl.tile_counts); a.ntiles = ntiles;
         lds = (size_t)ntiles * 4;
-        static bool raised[FDGS_MAX_DEVICES] = {};
-        bool& up = raised[current_device_slot()];
+        static bool raised[2][FDGS_MAX_DEVICES] = {};
+        bool& up = raised[antialiasing ? 1 : 0][current_device_slot()];
         if (!up) {
-            FDGS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, TILE_FORM1_MAX_TILES * 4));
+            FDGS_HIP_CHECK(hipFuncSetAttribute(antialiasing ? reinterpret_cast<const void*>(preprocess_fwd_kernel<true, true>)
+                                                            : reinterpret_cast<const void*>(preprocess_fwd_kernel<true, false>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, TILE_FORM1_MAX_TILES * 4));
             up = true;
         }
     }
-    { FDGS_TIMED("preprocess_fwd", stream); hipLaunchKernelGGL(count_tiles ? preprocess_fwd_kernel<true> : preprocess_fwd_kernel<false>, dim3(cdiv(p->P, 256)), dim3(256), lds, stream, a); }
+    {
+        FDGS_TIMED("preprocess_fwd", stream);
+        if (antialiasing) launch_preprocess_fwd<true>(stream, count_tiles, p->P, lds, a);
+        else launch_preprocess_fwd<false>(stream, count_tiles, p->P, lds, a);
+    }
     FDGS_LAUNCH_CHECK("preprocess_fwd", p->debug, stream);
     return FDGS_OK;
 }
@@ -641,10 +674,15 @@ extern "C" int fdgs_preprocess_fwd(void* stream_, const fdgs_raster_params* p, v
     return fdgs_preprocess_fwd_impl(stream_, p, geom, radii, nullptr);
 }
 
+extern "C" int fdgs_preprocess_fwd_aa(void* stream_, const fdgs_raster_params* p, void* geom, int32_t* radii) {
+    return fdgs_preprocess_fwd_impl(stream_, p, geom, radii, nullptr, false, true);
+}
+
 // called from fdgs_raster_bwd (render.hip)
 int fdgs_launch_preprocess_bwd(hipStream_t stream, const fdgs_raster_params* p, const void* geom,
-                               const fdgs_raster_grads* g) {
+                               const fdgs_raster_grads* g, bool antialiasing) {
     if (p->P == 0) return FDGS_OK;
+    FDGS_REQUIRE(!antialiasing || p->opacities, "opacities is NULL (an antialiased frame's backward reads them)");
     GeomLayout gl = geom_layout(p->P);
     PreBwdArgs a{};
     fill_frame_head(a, p);
@@ -665,8 +703,10 @@ int fdgs_launch_preprocess_bwd(hipStream_t stream, const fdgs_raster_params* p, 
     }
     {
         FDGS_TIMED("preprocess_bwd", stream);
-        if (e) hipLaunchKernelGGL(preprocess_bwd_kernel<true>, dim3(cdiv(e->Npad, 256)), dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL(preprocess_bwd_kernel<false>, dim3(cdiv(p->P, 256)), dim3(256), 0, stream, a);
+        void (*const epi)(PreBwdArgs) = antialiasing ? preprocess_bwd_kernel<true, true> : preprocess_bwd_kernel<true, false>;
+        void (*const plain)(PreBwdArgs) = antialiasing ? preprocess_bwd_kernel<false, true> : preprocess_bwd_kernel<false, false>;
+        if (e) hipLaunchKernelGGL(epi, dim3(cdiv(e->Npad, 256)), dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL(plain, dim3(cdiv(p->P, 256)), dim3(256), 0, stream, a);
     }
     FDGS_LAUNCH_CHECK("preprocess_bwd", p->debug, stream);
     return FDGS_OK;
@@ -687,11 +727,14 @@ extern "C" int fdgs_mark_visible(void* stream_, int P, const float* means3D, con
 // A loop over the Gaussians on the CPU around the functions of gs_math.h the kernels above call, in the kernels' order, with host pointers.
 // No arithmetic of their own: what they return is what gs_math.h computes (host rounding: no contraction, the kernels may fuse).
 
-extern "C" int fdgs_preprocess_host(const fdgs_raster_params* p, int32_t* radii, float* xy, float* conic, float* depth, float* rgb,
-                                    uint32_t* clamped, float* cov3D, uint32_t* rect, uint32_t* tiles) {
+// AA: the *_aa twins -- opacity_eff[P] = opacity * h as the kernel writes it into recB.y (0 for a culled Gaussian)
+template <bool AA>
+static int preprocess_host_impl(const fdgs_raster_params* p, int32_t* radii, float* xy, float* conic, float* depth, float* rgb,
+                                uint32_t* clamped, float* cov3D, uint32_t* rect, uint32_t* tiles, float* opacity_eff) {
     int rc = validate_raster_params(p);
     if (rc) return rc;
     FDGS_REQUIRE(p->P == 0 || (radii && xy && conic && depth && rgb && clamped && cov3D && rect && tiles), "an output array is NULL");
+    if constexpr (AA) FDGS_REQUIRE(p->P == 0 || (opacity_eff && p->opacities), "opacity_eff or opacities is NULL");
     CamConst c;
     load_cam(c, p->viewmatrix, p->projmatrix, p->campos, p->W, p->H, p->tanfovx, p->tanfovy, p->scale_modifier, p->sh_degree, p->sh_coeffs);
     for (size_t i = 0; i < (size_t)p->P; i++) {
@@ -706,8 +749,10 @@ extern "C" int fdgs_preprocess_host(const fdgs_raster_params* p, int32_t* radii,
         xy[2 * i] = xy[2 * i + 1] = 0.f; rect[2 * i] = rect[2 * i + 1] = 0u;
         for (int k = 0; k < 3; k++) { conic[3 * i + k] = 0.f; rgb[3 * i + k] = 0.f; }
         for (int k = 0; k < 6; k++) cov3D[6 * i + k] = 0.f;
+        if constexpr (AA) opacity_eff[i] = 0.f;
         GeoOut g;
-        if (!project_gaussian(c, pos, c6, &g)) continue;
+        if (!project_gaussian<AA>(c, pos, c6, &g, p->scales + 3 * i, p->rotations + 4 * i, p->cov3D_precomp == nullptr)) continue;
+        if constexpr (AA) opacity_eff[i] = p->opacities[i] * g.aa;
         if (p->colors_precomp) {
             for (int k = 0; k < 3; k++) rgb[3 * i + k] = p->colors_precomp[3 * i + k];
         } else {
@@ -722,14 +767,27 @@ extern "C" int fdgs_preprocess_host(const fdgs_raster_params* p, int32_t* radii,
     return FDGS_OK;
 }
 
-extern "C" int fdgs_preprocess_bwd_host(const fdgs_raster_params* p, const uint32_t* tiles, const uint32_t* clamped, const float* cov3D,
-                                        const float* d_xy, const float* d_conic, const float* d_rgb, const float* d_depth,
-                                        float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
-                                        float* dL_dcov3D) {
+extern "C" int fdgs_preprocess_host(const fdgs_raster_params* p, int32_t* radii, float* xy, float* conic, float* depth, float* rgb,
+                                    uint32_t* clamped, float* cov3D, uint32_t* rect, uint32_t* tiles) {
+    return preprocess_host_impl<false>(p, radii, xy, conic, depth, rgb, clamped, cov3D, rect, tiles, nullptr);
+}
+
+extern "C" int fdgs_preprocess_host_aa(const fdgs_raster_params* p, int32_t* radii, float* xy, float* conic, float* depth, float* rgb,
+                                       uint32_t* clamped, float* cov3D, uint32_t* rect, uint32_t* tiles, float* opacity_eff) {
+    return preprocess_host_impl<true>(p, radii, xy, conic, depth, rgb, clamped, cov3D, rect, tiles, opacity_eff);
+}
+
+// AA: d_opacity[P] = the opacity sum of the accumulator line, dL/d(opacity * h); dL_dopacity[P] = h * d_opacity is returned as well
+template <bool AA>
+static int preprocess_bwd_host_impl(const fdgs_raster_params* p, const uint32_t* tiles, const uint32_t* clamped, const float* cov3D,
+                                    const float* d_xy, const float* d_conic, const float* d_rgb, const float* d_depth, const float* d_opacity,
+                                    float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
+                                    float* dL_dcov3D, float* dL_dopacity) {
     int rc = validate_raster_params(p);
     if (rc) return rc;
     const bool has_cov = p->cov3D_precomp != nullptr;
     FDGS_REQUIRE(p->P == 0 || (tiles && cov3D && d_xy && d_conic && d_rgb && dL_dmeans2D && dL_dmeans3D && dL_dcov3D), "an array is NULL");
+    if constexpr (AA) FDGS_REQUIRE(p->P == 0 || (d_opacity && dL_dopacity && p->opacities), "d_opacity, dL_dopacity or opacities is NULL");
     FDGS_REQUIRE(p->P == 0 || !p->shs || (clamped && dL_dsh), "SH inputs need clamped and dL_dsh");
     FDGS_REQUIRE(p->P == 0 || has_cov || (dL_dscales && dL_drotations), "scale/rotation inputs need dL_dscales and dL_drotations");
     CamConst c;
@@ -743,15 +801,24 @@ extern "C" int fdgs_preprocess_bwd_host(const fdgs_raster_params* p, const uint3
         const float dd = d_depth ? d_depth[i] : 0.f;
         const float* gxy = d_xy + 2 * i; const float* gco = d_conic + 3 * i; const float* grgb = d_rgb + 3 * i;
         // (the kernel's rule: a Gaussian without tiles, or with an all-zero line from the blending backward, writes zero rows)
+        const float go = AA ? d_opacity[i] : 0.f;       // (the line's opacity word: part of the kernel's test)
         const bool any_grad = gxy[0] != 0.f || gxy[1] != 0.f || gco[0] != 0.f || gco[1] != 0.f || gco[2] != 0.f || grgb[0] != 0.f ||
-                              grgb[1] != 0.f || grgb[2] != 0.f || dd != 0.f;
+                              grgb[1] != 0.f || grgb[2] != 0.f || dd != 0.f || go != 0.f;
+        float dop = 0.f;
         if (tiles[i] != 0 && any_grad) {
             const float* pos = p->means3D + 3 * i;
             mean2d_grad_to_ndc(gxy[0], gxy[1], p->W, p->H, m2d);
-            project_bwd(c, pos, cov3D + 6 * i, gco, dd, m2d[0], m2d[1], dmean, dcov6);
+            if constexpr (AA) {
+                float h;
+                project_bwd<true>(c, pos, cov3D + 6 * i, gco, dd, m2d[0], m2d[1], dmean, dcov6, go * p->opacities[i], &h);
+                dop = h * go;
+            } else {
+                project_bwd(c, pos, cov3D + 6 * i, gco, dd, m2d[0], m2d[1], dmean, dcov6);
+            }
             if (p->shs) sh_bwd(c.D, p->shs + i * (size_t)M * 3, pos, c.campos, clamped[i], grgb, dsh, dmean);
             if (!has_cov) cov3d_bwd(p->scales + 3 * i, c.scale_mod, p->rotations + 4 * i, dcov6, ds, dq);
         }
+        if constexpr (AA) dL_dopacity[i] = dop;
         for (int k = 0; k < 3; k++) { dL_dmeans2D[3 * i + k] = m2d[k]; dL_dmeans3D[3 * i + k] = dmean[k]; }
         for (int k = 0; k < 6; k++) dL_dcov3D[6 * i + k] = dcov6[k];
         if (p->shs) for (int k = 0; k < M * 3; k++) dL_dsh[i * (size_t)M * 3 + k] = dsh[k];
@@ -763,6 +830,22 @@ extern "C" int fdgs_preprocess_bwd_host(const fdgs_raster_params* p, const uint3
     return FDGS_OK;
 }
 
+extern "C" int fdgs_preprocess_bwd_host(const fdgs_raster_params* p, const uint32_t* tiles, const uint32_t* clamped, const float* cov3D,
+                                        const float* d_xy, const float* d_conic, const float* d_rgb, const float* d_depth,
+                                        float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
+                                        float* dL_dcov3D) {
+    return preprocess_bwd_host_impl<false>(p, tiles, clamped, cov3D, d_xy, d_conic, d_rgb, d_depth, nullptr, dL_dmeans2D, dL_dmeans3D, dL_dsh,
+                                           dL_dscales, dL_drotations, dL_dcov3D, nullptr);
+}
+
+extern "C" int fdgs_preprocess_bwd_host_aa(const fdgs_raster_params* p, const uint32_t* tiles, const uint32_t* clamped, const float* cov3D,
+                                           const float* d_xy, const float* d_conic, const float* d_rgb, const float* d_depth,
+                                           const float* d_opacity, float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dsh, float* dL_dscales,
+                                           float* dL_drotations, float* dL_dcov3D, float* dL_dopacity) {
+    return preprocess_bwd_host_impl<true>(p, tiles, clamped, cov3D, d_xy, d_conic, d_rgb, d_depth, d_opacity, dL_dmeans2D, dL_dmeans3D, dL_dsh,
+                                          dL_dscales, dL_drotations, dL_dcov3D, dL_dopacity);
+}
+
 // ---- the camera's gradient (include/fdgs.h: fdgs_camera_grad_scratch_bytes, fdgs_camera_grad, fdgs_camera_grad_host) ---------------------
 
 extern "C" int fdgs_camera_grad_scratch_bytes(int P, size_t* bytes) {
@@ -772,8 +855,9 @@ extern "C" int fdgs_camera_grad_scratch_bytes(int P, size_t* bytes) {
     return FDGS_OK;
 }
 
-extern "C" int fdgs_camera_grad(void* stream_, const fdgs_raster_params* p, const void* geom, const float* scratch_acc, void* scratch,
-                                float* out) {
+// fdgs_camera_grad and fdgs_camera_grad_aa (the state was projected with the opacity compensation)
+static int camera_grad_impl(void* stream_, const fdgs_raster_params* p, const void* geom, const float* scratch_acc, void* scratch, float* out,
+                            bool antialiasing) {
     int rc = validate_raster_params(p);
     if (rc) return rc;
     FDGS_REQUIRE(out != nullptr, "out is NULL");
@@ -790,21 +874,39 @@ extern "C" int fdgs_camera_grad(void* stream_, const fdgs_raster_params* p, cons
     fill_frame_head(a, p);
     a.cov3D = at<float>(geom, gl.cov3D); a.tiles = at<uint32_t>(geom, gl.tiles); a.clamped = at<uint32_t>(geom, gl.clamped);
     a.gacc = scratch_acc; a.partial = static_cast<float*>(scratch);
+    FDGS_REQUIRE(!antialiasing || p->opacities, "opacities is NULL (an antialiased frame's camera gradient reads them)");
+    a.opacities = p->opacities;
     const int rows = cdiv(p->P, 256);
-    { FDGS_TIMED("camera_grad_partial", stream); hipLaunchKernelGGL(camera_grad_partial_kernel, dim3(rows), dim3(256), 0, stream, a); }
+    {
+        FDGS_TIMED("camera_grad_partial", stream);
+        hipLaunchKernelGGL(antialiasing ? camera_grad_partial_kernel<true> : camera_grad_partial_kernel<false>, dim3(rows), dim3(256), 0, stream, a);
+    }
     FDGS_LAUNCH_CHECK("camera_grad_partial", p->debug, stream);
     { FDGS_TIMED("camera_grad_final", stream); hipLaunchKernelGGL(camera_grad_final_kernel, dim3(1), dim3(256), 0, stream, a.partial, rows, out); }
     FDGS_LAUNCH_CHECK("camera_grad_final", p->debug, stream);
     return FDGS_OK;
 }
 
-// Host twin: the loop of fdgs_preprocess_bwd_host around camera_terms, summed in double.
-extern "C" int fdgs_camera_grad_host(const fdgs_raster_params* p, const uint32_t* tiles, const uint32_t* clamped, const float* cov3D,
-                                     const float* d_xy, const float* d_conic, const float* d_rgb, const float* d_depth, double* out) {
+extern "C" int fdgs_camera_grad(void* stream_, const fdgs_raster_params* p, const void* geom, const float* scratch_acc, void* scratch,
+                                float* out) {
+    return camera_grad_impl(stream_, p, geom, scratch_acc, scratch, out, false);
+}
+
+extern "C" int fdgs_camera_grad_aa(void* stream_, const fdgs_raster_params* p, const void* geom, const float* scratch_acc, void* scratch,
+                                   float* out) {
+    return camera_grad_impl(stream_, p, geom, scratch_acc, scratch, out, true);
+}
+
+// Host twin: the loop of fdgs_preprocess_bwd_host around camera_terms, summed in double.  AA: d_opacity as fdgs_preprocess_bwd_host_aa.
+template <bool AA>
+static int camera_grad_host_impl(const fdgs_raster_params* p, const uint32_t* tiles, const uint32_t* clamped, const float* cov3D,
+                                 const float* d_xy, const float* d_conic, const float* d_rgb, const float* d_depth, const float* d_opacity,
+                                 double* out) {
     int rc = validate_raster_params(p);
     if (rc) return rc;
     FDGS_REQUIRE(out != nullptr, "out is NULL");
     FDGS_REQUIRE(p->P == 0 || (tiles && cov3D && d_xy && d_conic && d_rgb), "an array is NULL");
+    if constexpr (AA) FDGS_REQUIRE(p->P == 0 || (d_opacity && p->opacities), "d_opacity or opacities is NULL");
     FDGS_REQUIRE(p->P == 0 || !p->shs || clamped, "SH inputs need clamped");
     double sum[CAM_TERMS];
     for (int k = 0; k < CAM_TERMS; k++) sum[k] = 0.0;
@@ -814,13 +916,14 @@ extern "C" int fdgs_camera_grad_host(const fdgs_raster_params* p, const uint32_t
     for (size_t i = 0; i < (size_t)p->P; i++) {
         const float dd = d_depth ? d_depth[i] : 0.f;
         const float* gxy = d_xy + 2 * i; const float* gco = d_conic + 3 * i; const float* grgb = d_rgb + 3 * i;
+        const float go = AA ? d_opacity[i] : 0.f;
         const bool any_grad = gxy[0] != 0.f || gxy[1] != 0.f || gco[0] != 0.f || gco[1] != 0.f || gco[2] != 0.f || grgb[0] != 0.f ||
-                              grgb[1] != 0.f || grgb[2] != 0.f || dd != 0.f;
+                              grgb[1] != 0.f || grgb[2] != 0.f || dd != 0.f || go != 0.f;
         if (tiles[i] == 0 || !any_grad) continue;
         float m2d[2], t[CAM_TERMS];
         mean2d_grad_to_ndc(gxy[0], gxy[1], p->W, p->H, m2d);
-        camera_terms(c, p->means3D + 3 * i, cov3D + 6 * i, gco, dd, m2d[0], m2d[1], p->shs ? p->shs + i * (size_t)M * 3 : nullptr,
-                     p->shs ? clamped[i] : 0u, grgb, t);
+        camera_terms<AA>(c, p->means3D + 3 * i, cov3D + 6 * i, gco, dd, m2d[0], m2d[1], p->shs ? p->shs + i * (size_t)M * 3 : nullptr,
+                         p->shs ? clamped[i] : 0u, grgb, t, AA ? go * p->opacities[i] : 0.f);
         for (int k = 0; k < CAM_TERMS; k++) sum[k] += (double)t[k];
     }
     for (int j = 0; j < 48; j++) out[j] = 0.0;
@@ -831,4 +934,15 @@ extern "C" int fdgs_camera_grad_host(const fdgs_raster_params* p, const uint32_t
         }
     for (int k = 0; k < 3; k++) out[32 + k] = sum[24 + k];
     return FDGS_OK;
+}
+
+extern "C" int fdgs_camera_grad_host(const fdgs_raster_params* p, const uint32_t* tiles, const uint32_t* clamped, const float* cov3D,
+                                     const float* d_xy, const float* d_conic, const float* d_rgb, const float* d_depth, double* out) {
+    return camera_grad_host_impl<false>(p, tiles, clamped, cov3D, d_xy, d_conic, d_rgb, d_depth, nullptr, out);
+}
+
+extern "C" int fdgs_camera_grad_host_aa(const fdgs_raster_params* p, const uint32_t* tiles, const uint32_t* clamped, const float* cov3D,
+                                        const float* d_xy, const float* d_conic, const float* d_rgb, const float* d_depth,
+                                        const float* d_opacity, double* out) {
+    return camera_grad_host_impl<true>(p, tiles, clamped, cov3D, d_xy, d_conic, d_rgb, d_depth, d_opacity, out);
 }

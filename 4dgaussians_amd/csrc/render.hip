@@ -1194,9 +1194,10 @@ extern "C" int fdgs_render_contrib(void* stream_, const fdgs_raster_params* p, c
     return FDGS_OK;
 }
 
-// fdgs_raster_bwd (dL_dalpha == nullptr) and fdgs_raster_bwd_alpha
+// fdgs_raster_bwd (dL_dalpha == nullptr), fdgs_raster_bwd_alpha and fdgs_raster_bwd_aa (antialiasing: the blending backward is the same --
+// its opacity sum is then the gradient of the compensated opacity -- and the per-Gaussian chain rule carries the compensation's)
 static int raster_bwd_impl(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img, uint32_t R,
-                           const fdgs_raster_grads* g, const float* dL_dalpha) {
+                           const fdgs_raster_grads* g, const float* dL_dalpha, bool antialiasing = false) {
     int rc = validate_raster_params(p);
     if (rc) return rc;
     FDGS_REQUIRE(g && geom && img && (binning || R == 0), "NULL buffer");
@@ -1235,7 +1236,7 @@ static int raster_bwd_impl(void* stream_, const fdgs_raster_params* p, const voi
         }
         FDGS_LAUNCH_CHECK("render_bwd", p->debug, stream);
     }
-    return fdgs_launch_preprocess_bwd(stream, p, geom, g);
+    return fdgs_launch_preprocess_bwd(stream, p, geom, g, antialiasing);
 }
 
 extern "C" int fdgs_raster_bwd(void* stream_,const fdgs_raster_params* p, const void* geom, const void* binning,
@@ -1246,4 +1247,9 @@ extern "C" int fdgs_raster_bwd(void* stream_,const fdgs_raster_params* p, const 
 extern "C" int fdgs_raster_bwd_alpha(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning,
                                      const void* img, uint32_t R, const fdgs_raster_grads* g, const float* dL_dalpha) {
     return raster_bwd_impl(stream_, p, geom, binning, img, R, g, dL_dalpha);
+}
+
+extern "C" int fdgs_raster_bwd_aa(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning,
+                                  const void* img, uint32_t R, const fdgs_raster_grads* g, const float* dL_dalpha) {
+    return raster_bwd_impl(stream_, p, geom, binning, img, R, g, dL_dalpha, true);
 }

@@ -186,18 +186,20 @@ def _render_state(who, frame_at, sh_degree, device, to_stored, to_model, viewpoi
         raise NotImplementedError(f"{who}: pipe.compute_cov3D_python / pipe.convert_SHs_python need the live model; use fdgs.render")
     with torch.no_grad():
         raster_settings, frame_time = _renderer._frame_settings(viewpoint_camera, cam_type, bg_color, scaling_modifier, sh_degree, device, pipe)
-        return _state_frame(frame_at(frame_time), raster_settings, to_stored, to_model, override_color, rgb8)[0]
+        return _state_frame(frame_at(frame_time), raster_settings, to_stored, to_model, override_color, rgb8, pipe)[0]
 
 
-def _state_frame(st, raster_settings, to_stored, to_model, override_color, rgb8):
-    """(result dict, RasterState) of the forward-only frame of the BakedFrame `st`: what _render_state returns, and what it leaves behind."""
+def _state_frame(st, raster_settings, to_stored, to_model, override_color, rgb8, pipe=None):
+    """(result dict, RasterState) of the forward-only frame of the BakedFrame `st`: what _render_state returns, and what it leaves behind.
+    `pipe.antialiasing`: the frame is projected with the opacity compensation, as render() projects it (the replay passes read the state)."""
     shs, colors = st.shs, None
     if override_color is not None:
         shs, colors = None, override_color.detach().float()
         if to_stored is not None:
             colors = to_stored(colors)
     image, radii, depth, rstate = _rasterizer.rasterize_forward(raster_settings, st.xyz, shs, colors, st.opacity, st.scales, st.rotations,
-                                                                None, expect_backward=False)
+                                                                None, expect_backward=False,
+                                                                **({"antialiasing": True} if _renderer._wants_antialiasing(pipe) else {}))
     vis = rstate.visibility
     if to_model is not None:
         radii = to_model(radii)
@@ -234,7 +236,7 @@ def _render_motion_state(who, owner, frame_at, sh_degree, device, to_stored, to_
         xyz_to, zero_bg = owner._motion_bufs
         xyz_to.copy_(frame_at(t_to).xyz)          # (the next state_at may overwrite the scratch / working state this one lives in)
         st = frame_at(frame_time)
-        out, rstate = _state_frame(st, raster_settings, to_stored, to_model, None, rgb8)
+        out, rstate = _state_frame(st, raster_settings, to_stored, to_model, None, rgb8, pipe)
         p = rstate.params
         W, H = int(p.W), int(p.H)
         view_at, proj_at = rstate.keep[8], rstate.keep[9]
@@ -289,7 +291,7 @@ def _render_pick_state(who, owner, frame_at, sh_degree, device, to_stored, to_mo
         if owner._pick_row_map is None:          # (stays None for rows stored in the model's order: there is nothing to build)
             owner._pick_row_map = owner._make_pick_row_map()
         row_map = owner._pick_row_map
-        out, rstate = _state_frame(frame_at(frame_time), raster_settings, to_stored, to_model, None, rgb8)
+        out, rstate = _state_frame(frame_at(frame_time), raster_settings, to_stored, to_model, None, rgb8, pipe)
         p = rstate.params
         W, H = int(p.W), int(p.H)
         ids = torch.empty(2, H, W, dtype=torch.int32, device=device)
@@ -408,7 +410,7 @@ def _render_contrib_state(who, owner, frame_at, sh_degree, device, to_stored, to
             pixel_weight = pixel_weight.detach().contiguous()
         if owner._pick_row_map is None:          # (stays None for rows stored in the model's order: there is nothing to build)
             owner._pick_row_map = owner._make_pick_row_map()
-        out, rstate = _state_frame(frame_at(frame_time), raster_settings, to_stored, to_model, None, rgb8)
+        out, rstate = _state_frame(frame_at(frame_time), raster_settings, to_stored, to_model, None, rgb8, pipe)
         if into.N > 0:
             _lib.check(_lib.lib().fdgs_render_contrib(_lib.stream_ptr(), rstate.params, _lib.ptr(rstate.geom), _lib.ptr(rstate.binning),
                                                       _lib.ptr(rstate.img), rstate.capacity, _lib.ptr(pixel_weight),
@@ -494,7 +496,7 @@ def _render_features_state(who, owner, frame_at, sh_degree, device, to_stored, t
         raster_settings, frame_time = _renderer._frame_settings(viewpoint_camera, cam_type, bg_color, scaling_modifier, sh_degree, device, pipe)
         if owner._pick_row_map is None:          # (stays None for rows stored in the model's order: there is nothing to build)
             owner._pick_row_map = owner._make_pick_row_map()
-        out, rstate = _state_frame(frame_at(frame_time), raster_settings, to_stored, to_model, None, rgb8)
+        out, rstate = _state_frame(frame_at(frame_time), raster_settings, to_stored, to_model, None, rgb8, pipe)
         p = rstate.params
         W, H = int(p.W), int(p.H)
         if owner.N == 0:                          # (an empty tensor has no address to hand over)

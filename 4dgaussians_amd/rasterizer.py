@@ -163,7 +163,7 @@ def _none_if_empty(t):
 class RasterState:
     """Buffers one forward pass leaves behind for its backward (the reference's geom/binning/img buffers).  `capacity` = the pair count
     the binning buffer is laid out for (what the C calls take as num_rendered); `num_rendered` = the true count (waits for it if needed)."""
-    __slots__ = ("params", "geom", "binning", "img", "capacity", "count", "keep", "visibility", "acc", "with_alpha")
+    __slots__ = ("params", "geom", "binning", "img", "capacity", "count", "keep", "visibility", "acc", "with_alpha", "antialiasing")
 
     def take_accumulator(self):
         """(buffer, zeroed) for fdgs_raster_grads::scratch_acc: the [P,16] accumulator the forward zero-filled on the way (training frames), once;
@@ -238,14 +238,17 @@ def _finish_exact(L, st, p, geom, img, cnt, color, depth, alpha=None):
 
 
 def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, out=None, expect_backward=False,
-                      want_alpha=False):
+                      want_alpha=False, antialiasing=False):
     """Runs stages 1-4 of include/fdgs.h. Returns (color, radii, depth, state).  `out` = (color [3,H,W], radii [P] int32, depth [1,H,W])
     buffers to write into (contiguous float32 / int32 on the device), e.g. slices of a batch tensor.  `expect_backward`: a training frame
     (the blending forward zero-fills the backward's accumulator on the way).  Which binning path runs: BINNING above -- every mode but the
     opt-in "capacity" returns the exact path's image.  `want_alpha`: the frame also delivers its accumulated opacity 1 - final_T; the result
     is then (color, radii, depth, alpha [1,H,W], state), `out` has the alpha buffer as its fourth entry and the backward of `state` runs
-    fdgs_raster_bwd_alpha (rasterize_backward's grad_alpha).  A frame that does not ask makes the C calls it always made."""
+    fdgs_raster_bwd_alpha (rasterize_backward's grad_alpha).  `antialiasing`: the projection compensates every opacity for the 0.3 px
+    dilation (opacity * h, include/fdgs.h: the *_aa entry points, which carry the optional alpha image themselves); the case is recorded on
+    `state`, whose backward and camera gradient follow it.  A frame that does not ask makes the C calls it always made."""
     global capacity_reruns
+    antialiasing = bool(antialiasing)
     L = _lib.lib()
     dev = means3D.device
     if not _is_hip_device(dev):
@@ -273,7 +276,10 @@ def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales,
         cap = (int(seen[0] * CAPACITY_SLACK) + 8192) // 4096 * 4096
         ctypes.c_uint32.from_address(cnt.addr).value = _SENTINEL
         binning = torch.empty(_bytes(L, "binning", cap, W, H), dtype=torch.uint8, device=dev)
-        if alpha is None:
+        if antialiasing:
+            check(L.fdgs_raster_fwd_capacity_aa(st, p, ptr(geom), ptr(binning), ptr(img), cap, _lib.c_void_p(cnt.addr), ptr(radii), ptr(color),
+                                                ptr(depth), ptr(alpha)))
+        elif alpha is None:
             check(L.fdgs_raster_fwd_capacity(st, p, ptr(geom), ptr(binning), ptr(img), cap, _lib.c_void_p(cnt.addr), ptr(radii), ptr(color), ptr(depth)))
         else:
             check(L.fdgs_raster_fwd_capacity_alpha(st, p, ptr(geom), ptr(binning), ptr(img), cap, _lib.c_void_p(cnt.addr), ptr(radii), ptr(color),
@@ -291,7 +297,7 @@ def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales,
                 capacity_reruns += 1
                 binning, cap = _finish_exact(L, st, p, geom, img, cnt, color, depth, alpha)
     else:
-        check(L.fdgs_preprocess_fwd(st, p, ptr(geom), ptr(radii)))
+        check((L.fdgs_preprocess_fwd_aa if antialiasing else L.fdgs_preprocess_fwd)(st, p, ptr(geom), ptr(radii)))
         check(L.fdgs_bin_prepare(st, p, ptr(geom), _lib.c_void_p(cnt.addr)))          # (blocks until the count is in host memory)
         cnt.R = ctypes.c_uint32.from_address(cnt.addr).value
         _note_count(cnt)
@@ -300,6 +306,7 @@ def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales,
     state = RasterState()
     state.params, state.geom, state.binning, state.img, state.capacity, state.count = p, geom, binning, img, cap, cnt
     state.visibility, state.acc, state.keep, state.with_alpha = vis, acc, tensors, alpha is not None
+    state.antialiasing = antialiasing
     if alpha is not None:
         return color, radii, depth, alpha, state
     return color, radii, depth, state
@@ -319,8 +326,12 @@ def fill_raster_grads(state, grad_color, grad_depth, d_means2D, epilogue=None):
 
 def raster_bwd_call(L, state, g, grad_alpha=None):
     """fdgs_raster_bwd of `state` on the filled fdgs_raster_grads `g`; a frame rendered with alpha (rasterize_forward's want_alpha) runs
-    fdgs_raster_bwd_alpha, with `grad_alpha` [1,H,W] (contiguous float32) or NULL where alpha did not reach the loss."""
-    if state.with_alpha:
+    fdgs_raster_bwd_alpha, with `grad_alpha` [1,H,W] (contiguous float32) or NULL where alpha did not reach the loss; an antialiased frame
+    (state.antialiasing) runs fdgs_raster_bwd_aa, which takes the same optional image."""
+    if getattr(state, "antialiasing", False):
+        check(L.fdgs_raster_bwd_aa(stream_ptr(), state.params, ptr(state.geom), ptr(state.binning), ptr(state.img), state.capacity, g,
+                                   ptr(grad_alpha) if state.with_alpha else None))
+    elif state.with_alpha:
         check(L.fdgs_raster_bwd_alpha(stream_ptr(), state.params, ptr(state.geom), ptr(state.binning), ptr(state.img), state.capacity, g,
                                       ptr(grad_alpha)))
     else:
@@ -337,12 +348,13 @@ def camera_wants_grad(settings):
 
 def camera_gradients(state, acc):
     """fdgs_camera_grad behind fdgs_raster_bwd of `state`, on the accumulator `acc` that call used -> [48] floats: dL/dviewmatrix [0,16),
-    dL/dprojmatrix [16,32), dL/dcampos [32,35) (include/fdgs.h).  Two launches, no atomics."""
+    dL/dprojmatrix [16,32), dL/dcampos [32,35) (include/fdgs.h).  Two launches, no atomics.  An antialiased state: fdgs_camera_grad_aa."""
     L = _lib.lib()
     p, dev = state.params, state.geom.device
     scratch = torch.empty(_bytes(L, "camera_grad_scratch", p.P), dtype=torch.uint8, device=dev)
     out = torch.empty(48, device=dev)
-    check(L.fdgs_camera_grad(stream_ptr(), p, ptr(state.geom), ptr(acc), ptr(scratch), ptr(out)))
+    call = L.fdgs_camera_grad_aa if getattr(state, "antialiasing", False) else L.fdgs_camera_grad
+    check(call(stream_ptr(), p, ptr(state.geom), ptr(acc), ptr(scratch), ptr(out)))
     return out
 
 
@@ -379,6 +391,14 @@ def rasterize_backward(state, grad_color, grad_depth=None, camera=False, grad_al
     return out
 
 
+def _frame_kw(want_alpha, antialiasing):
+    """rasterize_forward's keywords of a frame that asked for its alpha image and / or the opacity compensation; nothing otherwise."""
+    kw = {"want_alpha": True} if want_alpha else {}
+    if antialiasing:
+        kw["antialiasing"] = True
+    return kw
+
+
 def _image_grads(state, grad_color, grad_depth, grad_alpha):
     """(dL_dcolor, keywords of rasterize_backward) of a node's backward, or None where no image reached the loss.  A loss that saw depth or
     alpha but not the colour gets a zero colour image; a frame without alpha passes the keywords it always passed."""
@@ -393,10 +413,10 @@ def _image_grads(state, grad_color, grad_depth, grad_alpha):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_mode=True,
-                want_alpha=False):
+                want_alpha=False, antialiasing=False):
         *images, state = rasterize_forward(raster_settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                            expect_backward=bool(grad_mode) and any(ctx.needs_input_grad),
-                                           **({"want_alpha": True} if want_alpha else {}))
+                                           **_frame_kw(want_alpha, antialiasing))
         radii = images[1]
         ctx.state = state
         ctx.had = (sh is not None and sh.numel() > 0, colors_precomp is not None and colors_precomp.numel() > 0,
@@ -413,13 +433,13 @@ class _RasterizeGaussians(torch.autograd.Function):
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha=None):
         grads = _image_grads(ctx.state, grad_color, grad_depth, grad_alpha)
         if grads is None:               # no image reached the loss
-            return (None,) * 11
+            return (None,) * 12
         g = rasterize_backward(ctx.state, grads[0], grad_depth, **grads[1])
         had_sh, had_col, had_scale, had_cov = ctx.had
         op_shape, sh_shape = ctx.shapes
         return (g["means3D"], g["means2D"], g["shs"].reshape(sh_shape) if had_sh else None, g["colors"] if had_col else None,
                 g["opacities"].reshape(op_shape), g["scales"] if had_scale else None, g["rotations"] if had_scale else None,
-                g["cov3D"] if had_cov else None, None, None, None)
+                g["cov3D"] if had_cov else None, None, None, None, None)
 
 
 class _RasterizeGaussiansCamera(torch.autograd.Function):
@@ -429,9 +449,9 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix, campos,
-                raster_settings, want_alpha=False):
+                raster_settings, want_alpha=False, antialiasing=False):
         *images, state = rasterize_forward(raster_settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                           expect_backward=True, **({"want_alpha": True} if want_alpha else {}))
+                                           expect_backward=True, **_frame_kw(want_alpha, antialiasing))
         radii = images[1]
         ctx.state = state
         ctx.had = (sh is not None and sh.numel() > 0, colors_precomp is not None and colors_precomp.numel() > 0,
@@ -446,28 +466,35 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha=None):
         grads = _image_grads(ctx.state, grad_color, grad_depth, grad_alpha)
         if grads is None:
-            return (None,) * 13
+            return (None,) * 14
         g = rasterize_backward(ctx.state, grads[0], grad_depth, camera=True, **grads[1])
         had_sh, had_col, had_scale, had_cov = ctx.had
         op_shape, sh_shape = ctx.shapes
         cam = split_camera_gradients(g["camera"], *ctx.cam)
         return (g["means3D"], g["means2D"], g["shs"].reshape(sh_shape) if had_sh else None, g["colors"] if had_col else None,
                 g["opacities"].reshape(op_shape), g["scales"] if had_scale else None, g["rotations"] if had_scale else None,
-                g["cov3D"] if had_cov else None, *cam, None, None)
+                g["cov3D"] if had_cov else None, *cam, None, None, None)
 
 
-def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, render_alpha=False):
-    """-> (color, radii, depth), with `render_alpha` (color, radii, depth, alpha)."""
+def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, render_alpha=False,
+                        antialiasing=False):
+    """-> (color, radii, depth), with `render_alpha` (color, radii, depth, alpha).  `antialiasing`: every opacity is compensated for the
+    dilation of its footprint (rasterize_forward)."""
     if camera_wants_grad(raster_settings):
         rs = raster_settings
         return _RasterizeGaussiansCamera.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                               rs.viewmatrix, rs.projmatrix, rs.campos, rs, bool(render_alpha))
+                                               rs.viewmatrix, rs.projmatrix, rs.campos, rs, bool(render_alpha), bool(antialiasing))
     # (grad mode is read HERE: inside autograd.Function.forward it is always off and needs_input_grad stays True under torch.no_grad())
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                     raster_settings, torch.is_grad_enabled(), bool(render_alpha))
+                                     raster_settings, torch.is_grad_enabled(), bool(render_alpha), bool(antialiasing))
 
 
 class GaussianRasterizer(nn.Module):
+    # Opt-in opacity compensation of the 0.3 px dilation (upstream's `antialiasing`, gsplat's rasterize_mode="antialiased"): set it on the
+    # instance, `rasterizer.antialiasing = True`.  An attribute, not a constructor argument: the constructor's parameter list is pinned
+    # (tests/test_alpha_abi.py); rasterize_gaussians takes it as a keyword.
+    antialiasing = False
+
     def __init__(self, raster_settings, render_alpha=False):
         """`render_alpha`: forward also returns the accumulated opacity of every pixel, alpha [1,H,W] = 1 - final transmittance,
         differentiable like colour and depth -> (color, radii, depth, alpha)."""
@@ -493,4 +520,4 @@ class GaussianRasterizer(nn.Module):
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   self.raster_settings, self.render_alpha)
+                                   self.raster_settings, self.render_alpha, self.antialiasing)

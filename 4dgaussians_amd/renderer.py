@@ -1,7 +1,8 @@
 """Drop-in for `gaussian_renderer.render` of the reference (gaussian_renderer/__init__.py:18-138).
 
 Same signature, same result dict {"render","viewspace_points","visibility_filter","radii","depth"} (and, opt-in through
-`pipe.render_alpha = True`, "alpha": the accumulated opacity [1,H,W], differentiable); honours
+`pipe.render_alpha = True`, "alpha": the accumulated opacity [1,H,W], differentiable; `pipe.antialiasing = True` compensates every opacity
+for the 0.3 px dilation of its footprint, upstream's `antialiasing`); honours
 pipe.convert_SHs_python / pipe.compute_cov3D_python / pipe.debug and cam_type == "PanopticSports" exactly where the
 reference does.  When `pc._deformation` is this package's `deform_network`, the fine stage runs as two fused HIP
 stages: deform(+activations, + the cat of features_dc/features_rest) -> rasterize; no `time.repeat(N,1)` tensor, no
@@ -140,12 +141,18 @@ def _fused_backward(states, saved, grad_colors, grad_depths, camera=None, grad_a
 
 
 def _alpha_kw(cfg):
-    """rasterize_forward's keyword of a frame that asked for its alpha image (cfg["alpha"], from pipe.render_alpha); nothing otherwise."""
-    return {"want_alpha": True} if cfg.get("alpha") else {}
+    """rasterize_forward's keywords of a frame that asked for its alpha image (cfg["alpha"], from pipe.render_alpha) and / or the opacity
+    compensation (cfg["antialiasing"], from pipe.antialiasing); nothing otherwise."""
+    return _rasterizer._frame_kw(cfg.get("alpha"), cfg.get("antialiasing"))
 
 
 def _wants_alpha(pipe):
     return bool(getattr(pipe, "render_alpha", False))
+
+
+def _wants_antialiasing(pipe):
+    """Opt-in: every opacity is compensated for the 0.3 px dilation of its footprint (rasterizer.rasterize_forward's antialiasing)."""
+    return bool(getattr(pipe, "antialiasing", False))
 
 
 class _FusedRenderFunction(torch.autograd.Function):
@@ -304,6 +311,8 @@ def render_views(viewpoint_cameras, pc, pipe, bg_color, scaling_modifier=1.0, st
     cfg, perm, ins, net_ins = _fine_stage(pc, sinks)       # (the set in Hilbert order for this step where perm is not None)
     if _wants_alpha(pipe):
         cfg["alpha"] = True
+    if _wants_antialiasing(pipe):
+        cfg["antialiasing"] = True
     colors, radii, depths, *alphas = _FusedRenderViewsFunction.apply(cfg, times, settings, len(cams), *ins, *net_ins)
     if perm is not None:
         radii = torch.stack(_deformation.permute_rows(perm, [radii[v] for v in range(len(cams))], scatter=True))
@@ -366,6 +375,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         cfg, perm, ins, net_ins = _fine_stage(pc, (screenspace_points,) if torch.is_grad_enabled() else ())
         if want_alpha:
             cfg["alpha"] = True
+        if _wants_antialiasing(pipe):
+            cfg["antialiasing"] = True
         if cfg["grad"] and time_leaf is not None:
             rs = raster_settings
             rendered_image, radii, depth, vis, *alpha = _FusedRenderTimeFunction.apply(cfg, frame_time, rs, time_leaf, rs.viewmatrix, rs.projmatrix,
@@ -437,6 +448,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         shs_final = None
 
     rasterizer = GaussianRasterizer(raster_settings=raster_settings, render_alpha=want_alpha)       # (an nn.Module: only built on the paths that call it)
+    if _wants_antialiasing(pipe):
+        rasterizer.antialiasing = True
     rendered_image, radii, depth, *alpha = rasterizer(
         means3D=means3D_final, means2D=means2D, shs=shs_final, colors_precomp=colors_precomp, opacities=opacity_final,
         scales=scales_final, rotations=rotations_final, cov3D_precomp=cov3D_precomp)

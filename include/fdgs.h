@@ -220,6 +220,48 @@ int fdgs_raster_bwd(void* stream, const fdgs_raster_params* p, const void* geom,
 int fdgs_raster_bwd_alpha(void* stream, const fdgs_raster_params* p, const void* geom, const void* binning,
                           const void* img, uint32_t num_rendered, const fdgs_raster_grads* g, const float* dL_dalpha);
 
+/* Antialiased splatting: opacity compensation for the dilation (the EWA normalisation of Mip-Splatting; the upstream rasterizer's
+ * `antialiasing`, gsplat's rasterize_mode = "antialiased").  The projection adds 0.3 to the diagonal of every projected covariance, which
+ * widens a splat without lowering its peak: a splat far below a pixel blends much more than it carries.  With A, b, C the projected
+ * covariance before the dilation, a = A + 0.3, c = C + 0.3:
+ *       D0 = A C - b^2    D1 = a c - b^2    r = D0 / D1    h = sqrt(max(2.5e-5, r))        (the floor is upstream's)
+ * and the opacity the frame blends with is opacity * h.  It is what the projection kernel writes into recB.y (fdgs_geom_field 2) and what
+ * the exact tile culling sets its ellipse up from.  Nothing else changes: conic, radius, rect, depth, colour and every cull decision of the
+ * projection use the dilated covariance as before, so radii, visibility and densification statistics are those of the plain frame (only the
+ * pair count can fall: h <= 1 tightens the cull ellipse).
+ *   Forward: fdgs_preprocess_fwd_aa is fdgs_preprocess_fwd, fdgs_raster_fwd_capacity_aa is fdgs_raster_fwd_capacity_alpha (out_alpha opt),
+ *   with the compensation.  fdgs_bin_prepare, fdgs_bin_sort, fdgs_render_fwd(_alpha) and every replay pass (fdgs_render_pick,
+ *   fdgs_render_contrib, fdgs_render_features and its backward, the motion blend) are unchanged: they read recB and the cull mask the
+ *   projection wrote and nothing of the opacity input, so they follow an antialiased geom as it stands.
+ *   Backward: fdgs_raster_bwd_aa is fdgs_raster_bwd_alpha (dL_dalpha opt).  The blending backward is the same; its opacity sum is then
+ *   g = dL/d(opacity * h).  The per-Gaussian chain rule returns dL_dopacity = h * g (the epilogue: before the sigmoid's Jacobian) and, for r
+ *   above the floor, adds dL/dr = g * opacity / (2 h) through
+ *       dr/da = (C D1 - D0 c) / D1^2    dr/dc = (A D1 - D0 a) / D1^2    dr/db = 2 b (D0 - D1) / D1^2
+ *   to the covariance's gradient, from where it reaches dL_dcov3D, scales, rotations and the means like the conic's share (same clamp
+ *   conventions).  At or below the floor that path is exactly zero.  It reads p->opacities: the opacities the forward received.
+ *   fdgs_camera_grad_aa is fdgs_camera_grad of such a state (the compensation's share of the view matrix' gradient included).
+ *   A backward or camera-gradient call MUST take the case of the forward of its state: the state does not record it.
+ *   Host twins, as fdgs_preprocess_host / fdgs_preprocess_bwd_host / fdgs_camera_grad_host: fdgs_preprocess_host_aa also returns
+ *   opacity_eff[P] = opacity * h (0 for a culled Gaussian; it reads p->opacities), fdgs_preprocess_bwd_host_aa also takes d_opacity[P] (= g)
+ *   and returns dL_dopacity[P], fdgs_camera_grad_host_aa also takes d_opacity[P].
+ * The old entry points are the other case of the same implementation (a template switch on the kernels: they keep their instructions). */
+int fdgs_preprocess_fwd_aa(void* stream, const fdgs_raster_params* p, void* geom, int32_t* radii);
+int fdgs_raster_fwd_capacity_aa(void* stream, const fdgs_raster_params* p, void* geom, void* binning, void* img, uint32_t capacity,
+                                uint32_t* num_rendered_host, int32_t* radii, float* out_color, float* out_depth, float* out_alpha);
+int fdgs_raster_bwd_aa(void* stream, const fdgs_raster_params* p, const void* geom, const void* binning,
+                       const void* img, uint32_t num_rendered, const fdgs_raster_grads* g, const float* dL_dalpha);
+int fdgs_camera_grad_aa(void* stream, const fdgs_raster_params* p, const void* geom, const float* scratch_acc, void* scratch,
+                        float* out /* 48 floats, 16-byte aligned */);
+int fdgs_preprocess_host_aa(const fdgs_raster_params* p, int32_t* radii, float* xy, float* conic, float* depth, float* rgb,
+                            uint32_t* clamped, float* cov3D, uint32_t* rect, uint32_t* tiles, float* opacity_eff);
+int fdgs_preprocess_bwd_host_aa(const fdgs_raster_params* p, const uint32_t* tiles, const uint32_t* clamped, const float* cov3D,
+                                const float* d_xy, const float* d_conic, const float* d_rgb, const float* d_depth, const float* d_opacity,
+                                float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
+                                float* dL_dcov3D, float* dL_dopacity);
+int fdgs_camera_grad_host_aa(const fdgs_raster_params* p, const uint32_t* tiles, const uint32_t* clamped, const float* cov3D,
+                             const float* d_xy, const float* d_conic, const float* d_rgb, const float* d_depth, const float* d_opacity,
+                             double* out /* 48 */);
+
 /* Frustum test only (replaces _C.mark_visible): present[P] (uint8) = 1 where p_view.z > 0.2. */
 int fdgs_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                       uint8_t* present);
