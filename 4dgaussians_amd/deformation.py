@@ -674,9 +674,40 @@ def time_like(time):
     return tuple(time.shape), time.dtype, time.device
 
 
+# ---- the autograd nodes: one forward and one backward body, each class the signature its calls record around them -------------------------
+# Separate classes, so that a call whose time does not ask for a gradient records the node, with the inputs, it always recorded.
+
+def _node_forward(ctx, *impl_args):
+    """forward_impl(*impl_args) as an autograd node's forward -> (xyz, scales, rotations, opacity, shs)."""
+    ctx.st = st = forward_impl(*impl_args)
+    # outputs the backward needs go through save_for_backward: keeping them as plain attributes makes a reference
+    # cycle (output -> grad_fn -> ctx -> output) that only the cyclic GC breaks -- with ~1 GB of per-frame buffers
+    # hanging on it (saved activations) every frame then costs a fresh 1-GB hipMalloc (30 ms)
+    ctx.save_for_backward(st.o_sc, st.o_rot, st.o_op)
+    outs = (st.o_xyz, st.o_sc, st.o_rot, st.o_op, st.o_sh)
+    st.o_xyz = st.o_sc = st.o_rot = st.o_op = st.o_sh = None
+    ctx.set_materialize_grads(False)   # unused outputs arrive as None -> NULL pointers, which the kernels skip
+    return outs
+
+
+def _node_backward(ctx, upstream, time_at=None):
+    """One gradient per input of the node: gradient_tuple fills the tail, from xyz on, nothing in front of it has a gradient.  `time_at`:
+    where the time tensor sits in a node that has it as an input (ctx.time_like); it gets fdgs_deform_time_grad's result, run behind the
+    same fdgs_deform_bwd."""
+    st = ctx.st
+    b = backward_prepare(st, *ctx.saved_tensors)
+    keep = [_lib.f32(u) for u in upstream]        # (what the queued launch reads)
+    g = b.g
+    g.g_xyz, g.g_scales, g.g_rotations, g.g_opacity, g.g_shs = map(ptr, keep)
+    grads = backward_run(st, b)
+    out = [None] * (len(ctx.needs_input_grad) - len(grads)) + list(grads)
+    if time_at is not None:
+        out[time_at] = time_gradient_like(time_gradient(st, b), ctx.time_like)
+    return tuple(out)
+
+
 class _DeformTimeFunction(torch.autograd.Function):
-    """_DeformFunction for a time that asks for its gradient: the time tensor is an input, fdgs_deform_time_grad runs behind the same
-    fdgs_deform_bwd.  A sibling, so that every other call runs the node and the C calls it always ran."""
+    """The node of a call whose time asks for its gradient: the time tensor is an input."""
 
     @staticmethod
     def forward(ctx, cfg, xyz, scales, rotations, opacity, sh_a, sh_b, time, aabb, *rest):
@@ -684,47 +715,19 @@ class _DeformTimeFunction(torch.autograd.Function):
             t_tensor, t_scalar = None, float(time.detach().item())      # (the kernels take the frame time by value: one host read per forward)
         else:
             t_tensor, t_scalar = time, 0.0
-        st = forward_impl(cfg, t_scalar, xyz, scales, rotations, opacity, sh_a, sh_b, t_tensor, aabb, rest, True)
-        ctx.st, ctx.time_like = st, time_like(time)
-        ctx.save_for_backward(st.o_sc, st.o_rot, st.o_op)       # (see _DeformFunction.forward: no reference cycle through ctx)
-        outs = (st.o_xyz, st.o_sc, st.o_rot, st.o_op, st.o_sh)
-        st.o_xyz = st.o_sc = st.o_rot = st.o_op = st.o_sh = None
-        ctx.set_materialize_grads(False)
-        return outs
+        ctx.time_like = time_like(time)
+        return _node_forward(ctx, cfg, t_scalar, xyz, scales, rotations, opacity, sh_a, sh_b, t_tensor, aabb, rest, True)
 
     @staticmethod
-    def backward(ctx, g_xyz, g_sc, g_rot, g_op, g_sh):
-        st = ctx.st
-        o_sc, o_rot, o_op = ctx.saved_tensors
-        b = backward_prepare(st, o_sc, o_rot, o_op)
-        gx, gs, gr, go, gsh = map(_lib.f32, (g_xyz, g_sc, g_rot, g_op, g_sh))
-        g = b.g
-        g.g_xyz, g.g_scales, g.g_rotations, g.g_opacity, g.g_shs = ptr(gx), ptr(gs), ptr(gr), ptr(go), ptr(gsh)
-        grads = backward_run(st, b)
-        return (None,) + grads[:6] + (time_gradient_like(time_gradient(st, b), ctx.time_like),) + grads[7:]
+    def backward(ctx, *upstream):
+        return _node_backward(ctx, upstream, time_at=7)
 
 
 class _DeformFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg, t_scalar, xyz, scales, rotations, opacity, sh_a, sh_b, t_tensor, aabb, *rest):
-        st = forward_impl(cfg, t_scalar, xyz, scales, rotations, opacity, sh_a, sh_b, t_tensor, aabb, rest, any(ctx.needs_input_grad))
-        ctx.st = st
-        ctx.saved_act = st.saved_act
-        # outputs the backward needs go through save_for_backward: keeping them as plain attributes makes a reference
-        # cycle (output -> grad_fn -> ctx -> output) that only the cyclic GC breaks -- with ~1 GB of per-frame buffers
-        # hanging on it (saved activations) every frame then costs a fresh 1-GB hipMalloc (30 ms)
-        ctx.save_for_backward(st.o_sc, st.o_rot, st.o_op)
-        outs = (st.o_xyz, st.o_sc, st.o_rot, st.o_op, st.o_sh)
-        st.o_xyz = st.o_sc = st.o_rot = st.o_op = st.o_sh = None
-        ctx.set_materialize_grads(False)   # unused outputs arrive as None -> NULL pointers, which the kernels skip
-        return outs
+        return _node_forward(ctx, cfg, t_scalar, xyz, scales, rotations, opacity, sh_a, sh_b, t_tensor, aabb, rest, any(ctx.needs_input_grad))
 
     @staticmethod
-    def backward(ctx, g_xyz, g_sc, g_rot, g_op, g_sh):
-        st = ctx.st
-        o_sc, o_rot, o_op = ctx.saved_tensors
-        b = backward_prepare(st, o_sc, o_rot, o_op)
-        gx, gs, gr, go, gsh = map(_lib.f32, (g_xyz, g_sc, g_rot, g_op, g_sh))
-        g = b.g
-        g.g_xyz, g.g_scales, g.g_rotations, g.g_opacity, g.g_shs = ptr(gx), ptr(gs), ptr(gr), ptr(go), ptr(gsh)
-        return (None, None) + backward_run(st, b)
+    def backward(ctx, *upstream):
+        return _node_backward(ctx, upstream)

@@ -197,9 +197,9 @@ def _state_frame(st, raster_settings, to_stored, to_model, override_color, rgb8,
         shs, colors = None, override_color.detach().float()
         if to_stored is not None:
             colors = to_stored(colors)
+    opts = _rasterizer.FrameOptions.of(pipe)._replace(alpha=False)       # (a playback frame takes the projection's option only)
     image, radii, depth, rstate = _rasterizer.rasterize_forward(raster_settings, st.xyz, shs, colors, st.opacity, st.scales, st.rotations,
-                                                                None, expect_backward=False,
-                                                                **({"antialiasing": True} if _renderer._wants_antialiasing(pipe) else {}))
+                                                                None, expect_backward=False, **opts.keywords())
     vis = rstate.visibility
     if to_model is not None:
         radii = to_model(radii)

@@ -47,6 +47,47 @@ class GaussianRasterizationSettings(NamedTuple):
     debug: bool
 
 
+class FrameOptions(NamedTuple):
+    """What a frame asks of the rasterizer beyond colour, radii and depth; all off: the frame the reference renders.  `alpha`: the frame also
+    delivers its accumulated opacity 1 - final_T.  `antialiasing`: the projection compensates every opacity for the 0.3 px dilation of its
+    footprint.  Built once per frame and handed on as itself; which C entry point each stage then calls: _stage_call."""
+    alpha: bool = False
+    antialiasing: bool = False
+
+    @classmethod
+    def of(cls, source):
+        """The options `source` asks for through its attributes `render_alpha` and `antialiasing`: the `pipe` of render() (absent: off), a
+        GaussianRasterizer."""
+        return cls(bool(getattr(source, "render_alpha", False)), bool(getattr(source, "antialiasing", False)))
+
+    def keywords(self):
+        """rasterize_forward's keywords for what the frame asked.  A frame that asked for nothing passes none: its call is the one that
+        function, and whatever a test puts in its place, has always received."""
+        return {k: True for k, v in (("want_alpha", self.alpha), ("antialiasing", self.antialiasing)) if v}
+
+
+PLAIN = FrameOptions()
+
+# The suffixed forms each stage has beside its plain entry point (include/fdgs.h), and the one rule that picks among them:
+#   antialiased -> the _aa form; it always takes the alpha image as its last argument, NULL where the frame did not ask for one;
+#   alpha only  -> the _alpha form, with the image;
+#   neither     -> the plain form, without the argument.
+# The projection and the camera gradient have no alpha image, hence no _alpha form and no such argument; the blend has no _aa form: the
+# projection carries the compensation, an antialiased frame blends like any other.
+_STAGE_FORMS = {"preprocess_fwd": ("_aa",), "raster_fwd_capacity": ("_aa", "_alpha"), "render_fwd": ("_alpha",),
+                "raster_bwd": ("_aa", "_alpha"), "camera_grad": ("_aa",)}
+
+
+def _stage_call(L, stage, opts, args, alpha=None):
+    """fdgs_<stage> in the form `opts` selects, on `args`; `alpha`: the pointer of the alpha image (or of its gradient), for the forms that
+    take one."""
+    forms = _STAGE_FORMS[stage]
+    form = "_aa" if opts.antialiasing and "_aa" in forms else "_alpha" if opts.alpha and "_alpha" in forms else ""
+    if form and "_alpha" in forms:
+        args += (alpha,)
+    check(getattr(L, "fdgs_" + stage + form)(*args))
+
+
 # ---- pair-count bookkeeping of the binning stage -------------------------------------------------------------------------------------
 # The reference's rasterizer reads the number of (tile, Gaussian) pairs back to the host in the middle of every forward (to size its
 # binning buffer), with nothing queued behind the read: host and device wait for each other once per frame.  Here, once a pair count has
@@ -177,6 +218,21 @@ class RasterState:
     def num_rendered(self):
         return int(self.count.value())
 
+    @property
+    def options(self):
+        """The FrameOptions this frame was rendered with.  Read from the two slots on every call: the backward and the camera gradient
+        follow the state as it is when they run."""
+        return FrameOptions(self.with_alpha, self.antialiasing)
+
+
+def _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp):
+    """The reference's two input checks (its messages, typo included): one colour source, one covariance source."""
+    if (shs is None) == (colors_precomp is None):
+        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+            ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+        raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+
 
 def _frame_params(settings, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp):
     """(fdgs_raster_params of one frame, the eleven tensors it points at).  The tensors are normalised first: float32 and contiguous on the
@@ -189,11 +245,7 @@ def _frame_params(settings, means3D, shs, colors_precomp, opacities, scales, rot
     bg, view = _f32(settings.bg, dev), _f32(settings.viewmatrix, dev)
     proj, campos = _f32(settings.projmatrix, dev), _f32(settings.campos, dev)
     if means3D.shape[0] > 0:         # (an empty set may come without either)
-        if (shs is None) == (colors_precomp is None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+        _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
     P = means3D.shape[0]
     p = RasterParams()
     p.P, p.sh_degree, p.W, p.H = P, int(settings.sh_degree), int(settings.image_width), int(settings.image_height)
@@ -225,15 +277,12 @@ def _claim_count(dev, key, P):
     return cnt, seen, pending
 
 
-def _finish_exact(L, st, p, geom, img, cnt, color, depth, alpha=None):
-    """Stages 3-4 on a binning buffer of the true size, cnt.R pairs (stages 1-2 are complete in `geom`) -> (binning, cnt.R).  `alpha`: the
-    frame asked for its accumulated opacity (the blend writes that image too)."""
+def _finish_exact(L, st, p, geom, img, cnt, opts, color, depth, alpha):
+    """Stages 3-4 on a binning buffer of the true size, cnt.R pairs (stages 1-2 are complete in `geom`) -> (binning, cnt.R).  A frame that
+    asked for its accumulated opacity has the blend write that image, `alpha`, too."""
     binning = torch.empty(_bytes(L, "binning", cnt.R, p.W, p.H), dtype=torch.uint8, device=geom.device)
     check(L.fdgs_bin_sort(st, p, ptr(geom), ptr(binning), ptr(img), cnt.R))
-    if alpha is None:
-        check(L.fdgs_render_fwd(st, p, ptr(geom), ptr(binning), ptr(img), cnt.R, ptr(color), ptr(depth)))
-    else:
-        check(L.fdgs_render_fwd_alpha(st, p, ptr(geom), ptr(binning), ptr(img), cnt.R, ptr(color), ptr(depth), ptr(alpha)))
+    _stage_call(L, "render_fwd", opts, (st, p, ptr(geom), ptr(binning), ptr(img), cnt.R, ptr(color), ptr(depth)), ptr(alpha))
     return binning, cnt.R
 
 
@@ -242,13 +291,13 @@ def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales,
     """Runs stages 1-4 of include/fdgs.h. Returns (color, radii, depth, state).  `out` = (color [3,H,W], radii [P] int32, depth [1,H,W])
     buffers to write into (contiguous float32 / int32 on the device), e.g. slices of a batch tensor.  `expect_backward`: a training frame
     (the blending forward zero-fills the backward's accumulator on the way).  Which binning path runs: BINNING above -- every mode but the
-    opt-in "capacity" returns the exact path's image.  `want_alpha`: the frame also delivers its accumulated opacity 1 - final_T; the result
-    is then (color, radii, depth, alpha [1,H,W], state), `out` has the alpha buffer as its fourth entry and the backward of `state` runs
-    fdgs_raster_bwd_alpha (rasterize_backward's grad_alpha).  `antialiasing`: the projection compensates every opacity for the 0.3 px
-    dilation (opacity * h, include/fdgs.h: the *_aa entry points, which carry the optional alpha image themselves); the case is recorded on
-    `state`, whose backward and camera gradient follow it.  A frame that does not ask makes the C calls it always made."""
+    opt-in "capacity" returns the exact path's image.  `want_alpha` and `antialiasing` are the frame's FrameOptions: with `want_alpha` the
+    result is (color, radii, depth, alpha [1,H,W], state), `out` has the alpha buffer as its fourth entry and the backward of `state` takes
+    the alpha image's gradient (rasterize_backward's grad_alpha); with `antialiasing` every opacity is compensated (opacity * h,
+    include/fdgs.h).  Both are recorded on `state`, whose backward and camera gradient follow it; which entry point each stage calls:
+    _stage_call.  A frame that does not ask makes the C calls it always made."""
     global capacity_reruns
-    antialiasing = bool(antialiasing)
+    opts = FrameOptions(bool(want_alpha), bool(antialiasing))
     L = _lib.lib()
     dev = means3D.device
     if not _is_hip_device(dev):
@@ -260,10 +309,10 @@ def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales,
     if out is None:
         out = (torch.empty(3, H, W, dtype=torch.float32, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
                torch.empty(1, H, W, dtype=torch.float32, device=dev))
-        if want_alpha:
+        if opts.alpha:
             out += (torch.empty(1, H, W, dtype=torch.float32, device=dev),)
     color, radii, depth = out[:3]
-    alpha = out[3] if want_alpha else None
+    alpha = out[3] if opts.alpha else None
     vis = torch.empty(P, dtype=torch.bool, device=dev)       # radii > 0, written by the projection kernel (no elementwise launch)
     p.visibility = ptr(vis)
     # a training frame: the blending forward zero-fills the backward's per-Gaussian accumulator on the way (no fill launch before the backward)
@@ -276,14 +325,8 @@ def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales,
         cap = (int(seen[0] * CAPACITY_SLACK) + 8192) // 4096 * 4096
         ctypes.c_uint32.from_address(cnt.addr).value = _SENTINEL
         binning = torch.empty(_bytes(L, "binning", cap, W, H), dtype=torch.uint8, device=dev)
-        if antialiasing:
-            check(L.fdgs_raster_fwd_capacity_aa(st, p, ptr(geom), ptr(binning), ptr(img), cap, _lib.c_void_p(cnt.addr), ptr(radii), ptr(color),
-                                                ptr(depth), ptr(alpha)))
-        elif alpha is None:
-            check(L.fdgs_raster_fwd_capacity(st, p, ptr(geom), ptr(binning), ptr(img), cap, _lib.c_void_p(cnt.addr), ptr(radii), ptr(color), ptr(depth)))
-        else:
-            check(L.fdgs_raster_fwd_capacity_alpha(st, p, ptr(geom), ptr(binning), ptr(img), cap, _lib.c_void_p(cnt.addr), ptr(radii), ptr(color),
-                                                   ptr(depth), ptr(alpha)))
+        _stage_call(L, "raster_fwd_capacity", opts, (st, p, ptr(geom), ptr(binning), ptr(img), cap, _lib.c_void_p(cnt.addr), ptr(radii), ptr(color),
+                                                     ptr(depth)), ptr(alpha))
         if BINNING == "capacity":      # opt-in: never waits; the count is looked at when a later frame starts
             cnt.capacity = cap
             cnt.stream = _current_stream(dev)
@@ -295,19 +338,19 @@ def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales,
             _note_count(cnt)
             if cnt.R > cap:            # the speculative frame dropped pairs: finish it exactly
                 capacity_reruns += 1
-                binning, cap = _finish_exact(L, st, p, geom, img, cnt, color, depth, alpha)
+                binning, cap = _finish_exact(L, st, p, geom, img, cnt, opts, color, depth, alpha)
     else:
-        check((L.fdgs_preprocess_fwd_aa if antialiasing else L.fdgs_preprocess_fwd)(st, p, ptr(geom), ptr(radii)))
+        _stage_call(L, "preprocess_fwd", opts, (st, p, ptr(geom), ptr(radii)))
         check(L.fdgs_bin_prepare(st, p, ptr(geom), _lib.c_void_p(cnt.addr)))          # (blocks until the count is in host memory)
         cnt.R = ctypes.c_uint32.from_address(cnt.addr).value
         _note_count(cnt)
-        binning, cap = _finish_exact(L, st, p, geom, img, cnt, color, depth, alpha)
+        binning, cap = _finish_exact(L, st, p, geom, img, cnt, opts, color, depth, alpha)
     _tls.st["last"] = cnt
     state = RasterState()
     state.params, state.geom, state.binning, state.img, state.capacity, state.count = p, geom, binning, img, cap, cnt
-    state.visibility, state.acc, state.keep, state.with_alpha = vis, acc, tensors, alpha is not None
-    state.antialiasing = antialiasing
-    if alpha is not None:
+    state.visibility, state.acc, state.keep = vis, acc, tensors
+    state.with_alpha, state.antialiasing = opts
+    if opts.alpha:
         return color, radii, depth, alpha, state
     return color, radii, depth, state
 
@@ -325,17 +368,10 @@ def fill_raster_grads(state, grad_color, grad_depth, d_means2D, epilogue=None):
 
 
 def raster_bwd_call(L, state, g, grad_alpha=None):
-    """fdgs_raster_bwd of `state` on the filled fdgs_raster_grads `g`; a frame rendered with alpha (rasterize_forward's want_alpha) runs
-    fdgs_raster_bwd_alpha, with `grad_alpha` [1,H,W] (contiguous float32) or NULL where alpha did not reach the loss; an antialiased frame
-    (state.antialiasing) runs fdgs_raster_bwd_aa, which takes the same optional image."""
-    if getattr(state, "antialiasing", False):
-        check(L.fdgs_raster_bwd_aa(stream_ptr(), state.params, ptr(state.geom), ptr(state.binning), ptr(state.img), state.capacity, g,
-                                   ptr(grad_alpha) if state.with_alpha else None))
-    elif state.with_alpha:
-        check(L.fdgs_raster_bwd_alpha(stream_ptr(), state.params, ptr(state.geom), ptr(state.binning), ptr(state.img), state.capacity, g,
-                                      ptr(grad_alpha)))
-    else:
-        check(L.fdgs_raster_bwd(stream_ptr(), state.params, ptr(state.geom), ptr(state.binning), ptr(state.img), state.capacity, g))
+    """fdgs_raster_bwd of `state` on the filled fdgs_raster_grads `g`, in the form state.options selects (_stage_call).  `grad_alpha`
+    [1,H,W] (contiguous float32): the gradient of the alpha image of a frame rendered with it, NULL where alpha did not reach the loss."""
+    _stage_call(L, "raster_bwd", state.options, (stream_ptr(), state.params, ptr(state.geom), ptr(state.binning), ptr(state.img), state.capacity, g),
+                ptr(grad_alpha if state.with_alpha else None))
 
 
 def camera_wants_grad(settings):
@@ -348,13 +384,13 @@ def camera_wants_grad(settings):
 
 def camera_gradients(state, acc):
     """fdgs_camera_grad behind fdgs_raster_bwd of `state`, on the accumulator `acc` that call used -> [48] floats: dL/dviewmatrix [0,16),
-    dL/dprojmatrix [16,32), dL/dcampos [32,35) (include/fdgs.h).  Two launches, no atomics.  An antialiased state: fdgs_camera_grad_aa."""
+    dL/dprojmatrix [16,32), dL/dcampos [32,35) (include/fdgs.h).  Two launches, no atomics.  An antialiased state: the form of it that
+    differentiates the compensation too (_stage_call)."""
     L = _lib.lib()
     p, dev = state.params, state.geom.device
     scratch = torch.empty(_bytes(L, "camera_grad_scratch", p.P), dtype=torch.uint8, device=dev)
     out = torch.empty(48, device=dev)
-    call = L.fdgs_camera_grad_aa if getattr(state, "antialiasing", False) else L.fdgs_camera_grad
-    check(call(stream_ptr(), p, ptr(state.geom), ptr(acc), ptr(scratch), ptr(out)))
+    _stage_call(L, "camera_grad", state.options, (stream_ptr(), p, ptr(state.geom), ptr(acc), ptr(scratch), ptr(out)))
     return out
 
 
@@ -391,102 +427,90 @@ def rasterize_backward(state, grad_color, grad_depth=None, camera=False, grad_al
     return out
 
 
-def _frame_kw(want_alpha, antialiasing):
-    """rasterize_forward's keywords of a frame that asked for its alpha image and / or the opacity compensation; nothing otherwise."""
-    kw = {"want_alpha": True} if want_alpha else {}
-    if antialiasing:
-        kw["antialiasing"] = True
-    return kw
+# ---- the autograd nodes ---------------------------------------------------------------------------------------------------------------
+# One forward and one backward body; each node class is the signature its frames record, around them.  Separate classes, so that a frame
+# that does not ask for the camera's gradient records the node, with the inputs, it always recorded.
+
+def _node_forward(ctx, raster_settings, gaussians, expect_backward, opts):
+    """`gaussians`: rasterize_forward's seven per-Gaussian inputs, in its order."""
+    _, sh, colors_precomp, opacities, scales, _, cov3Ds_precomp = gaussians
+    *images, state = rasterize_forward(raster_settings, *gaussians, expect_backward=expect_backward, **opts.keywords())
+    ctx.state = state
+    ctx.had = (sh is not None and sh.numel() > 0, colors_precomp is not None and colors_precomp.numel() > 0,
+               scales is not None and scales.numel() > 0, cov3Ds_precomp is not None and cov3Ds_precomp.numel() > 0)
+    ctx.shapes = (opacities.shape, None if sh is None else sh.shape)
+    ctx.mark_non_differentiable(images[1])      # radii
+    # an output the loss never used must arrive in backward as None, not as a materialised zero image: the
+    # reference's training loss ignores `depth` (train.py:201-214), and a NULL dL_ddepth selects the blending
+    # backward without the depth terms (render_bwd_kernel<false>, csrc/render.hip)
+    ctx.set_materialize_grads(False)
+    return tuple(images)        # (color, radii, depth) and, where asked for, alpha
 
 
-def _image_grads(state, grad_color, grad_depth, grad_alpha):
-    """(dL_dcolor, keywords of rasterize_backward) of a node's backward, or None where no image reached the loss.  A loss that saw depth or
-    alpha but not the colour gets a zero colour image; a frame without alpha passes the keywords it always passed."""
+def _node_backward(ctx, grad_color, grad_depth, grad_alpha, cam_at=None):
+    """One gradient per input of the node: the eight Gaussian tensors come first; `cam_at`: where viewmatrix, projmatrix and campos sit
+    (ctx.cam) in a node that has them as inputs.  A loss that saw depth or alpha but not the colour gets a zero colour image; rasterize_backward
+    is given only the keywords the frame needs."""
+    out = [None] * len(ctx.needs_input_grad)
     if grad_color is None:
-        if grad_depth is None and grad_alpha is None:
-            return None
+        if grad_depth is None and grad_alpha is None:       # no image reached the loss
+            return tuple(out)
         like = grad_depth if grad_depth is not None else grad_alpha
-        grad_color = torch.zeros(3, state.params.H, state.params.W, device=like.device)
-    return grad_color, ({"grad_alpha": grad_alpha} if getattr(state, "with_alpha", False) else {})
+        grad_color = torch.zeros(3, ctx.state.params.H, ctx.state.params.W, device=like.device)
+    kw = {} if cam_at is None else {"camera": True}
+    if grad_alpha is not None:
+        kw["grad_alpha"] = grad_alpha
+    g = rasterize_backward(ctx.state, grad_color, grad_depth, **kw)
+    had_sh, had_col, had_scale, had_cov = ctx.had
+    op_shape, sh_shape = ctx.shapes
+    out[:8] = (g["means3D"], g["means2D"], g["shs"].reshape(sh_shape) if had_sh else None, g["colors"] if had_col else None,
+               g["opacities"].reshape(op_shape), g["scales"] if had_scale else None, g["rotations"] if had_scale else None,
+               g["cov3D"] if had_cov else None)
+    if cam_at is not None:
+        out[cam_at:cam_at + 3] = split_camera_gradients(g["camera"], *ctx.cam)
+    return tuple(out)
 
 
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_mode=True,
-                want_alpha=False, antialiasing=False):
-        *images, state = rasterize_forward(raster_settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                           expect_backward=bool(grad_mode) and any(ctx.needs_input_grad),
-                                           **_frame_kw(want_alpha, antialiasing))
-        radii = images[1]
-        ctx.state = state
-        ctx.had = (sh is not None and sh.numel() > 0, colors_precomp is not None and colors_precomp.numel() > 0,
-                   scales is not None and scales.numel() > 0, cov3Ds_precomp is not None and cov3Ds_precomp.numel() > 0)
-        ctx.shapes = (opacities.shape, None if sh is None else sh.shape)
-        ctx.mark_non_differentiable(radii)
-        # an output the loss never used must arrive in backward as None, not as a materialised zero image: the
-        # reference's training loss ignores `depth` (train.py:201-214), and a NULL dL_ddepth selects the blending
-        # backward without the depth terms (render_bwd_kernel<false>, csrc/render.hip)
-        ctx.set_materialize_grads(False)
-        return tuple(images)        # (color, radii, depth) and, where asked for, alpha
+                opts=PLAIN):
+        return _node_forward(ctx, raster_settings, (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp),
+                             bool(grad_mode) and any(ctx.needs_input_grad), opts)
 
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha=None):
-        grads = _image_grads(ctx.state, grad_color, grad_depth, grad_alpha)
-        if grads is None:               # no image reached the loss
-            return (None,) * 12
-        g = rasterize_backward(ctx.state, grads[0], grad_depth, **grads[1])
-        had_sh, had_col, had_scale, had_cov = ctx.had
-        op_shape, sh_shape = ctx.shapes
-        return (g["means3D"], g["means2D"], g["shs"].reshape(sh_shape) if had_sh else None, g["colors"] if had_col else None,
-                g["opacities"].reshape(op_shape), g["scales"] if had_scale else None, g["rotations"] if had_scale else None,
-                g["cov3D"] if had_cov else None, None, None, None, None)
+        return _node_backward(ctx, grad_color, grad_depth, grad_alpha)
 
 
 class _RasterizeGaussiansCamera(torch.autograd.Function):
-    """_RasterizeGaussians for a frame whose camera asks for a gradient (camera_wants_grad): viewmatrix, projmatrix and campos of the
-    settings are inputs as well, and their gradients come from fdgs_camera_grad behind the same fdgs_raster_bwd.  A sibling, so that the
-    frames that do not ask run the node and the C calls they always ran.  The Gaussians may all be detached (tracking)."""
+    """The node of a frame whose camera asks for a gradient (camera_wants_grad): viewmatrix, projmatrix and campos of the settings are
+    inputs as well, and their gradients come from fdgs_camera_grad behind the same fdgs_raster_bwd.  The Gaussians may all be detached
+    (tracking)."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix, campos,
-                raster_settings, want_alpha=False, antialiasing=False):
-        *images, state = rasterize_forward(raster_settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                           expect_backward=True, **_frame_kw(want_alpha, antialiasing))
-        radii = images[1]
-        ctx.state = state
-        ctx.had = (sh is not None and sh.numel() > 0, colors_precomp is not None and colors_precomp.numel() > 0,
-                   scales is not None and scales.numel() > 0, cov3Ds_precomp is not None and cov3Ds_precomp.numel() > 0)
-        ctx.shapes = (opacities.shape, None if sh is None else sh.shape)
+                raster_settings, opts=PLAIN):
         ctx.cam = (viewmatrix, projmatrix, campos)        # (shape / dtype / device of the gradients to return; inputs of this node anyway)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
-        return tuple(images)
+        return _node_forward(ctx, raster_settings, (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp), True, opts)
 
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha=None):
-        grads = _image_grads(ctx.state, grad_color, grad_depth, grad_alpha)
-        if grads is None:
-            return (None,) * 14
-        g = rasterize_backward(ctx.state, grads[0], grad_depth, camera=True, **grads[1])
-        had_sh, had_col, had_scale, had_cov = ctx.had
-        op_shape, sh_shape = ctx.shapes
-        cam = split_camera_gradients(g["camera"], *ctx.cam)
-        return (g["means3D"], g["means2D"], g["shs"].reshape(sh_shape) if had_sh else None, g["colors"] if had_col else None,
-                g["opacities"].reshape(op_shape), g["scales"] if had_scale else None, g["rotations"] if had_scale else None,
-                g["cov3D"] if had_cov else None, *cam, None, None, None)
+        return _node_backward(ctx, grad_color, grad_depth, grad_alpha, cam_at=8)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, render_alpha=False,
                         antialiasing=False):
     """-> (color, radii, depth), with `render_alpha` (color, radii, depth, alpha).  `antialiasing`: every opacity is compensated for the
     dilation of its footprint (rasterize_forward)."""
+    opts = FrameOptions(bool(render_alpha), bool(antialiasing))
     if camera_wants_grad(raster_settings):
         rs = raster_settings
         return _RasterizeGaussiansCamera.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                               rs.viewmatrix, rs.projmatrix, rs.campos, rs, bool(render_alpha), bool(antialiasing))
+                                               rs.viewmatrix, rs.projmatrix, rs.campos, rs, opts)
     # (grad mode is read HERE: inside autograd.Function.forward it is always off and needs_input_grad stays True under torch.no_grad())
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                     raster_settings, torch.is_grad_enabled(), bool(render_alpha), bool(antialiasing))
+                                     raster_settings, torch.is_grad_enabled(), opts)
 
 
 class GaussianRasterizer(nn.Module):
@@ -514,10 +538,6 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None):
-        if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+        _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   self.raster_settings, self.render_alpha, self.antialiasing)
+                                   self.raster_settings, *FrameOptions.of(self))

@@ -17,7 +17,7 @@ import torch
 from . import _lib
 from . import deformation as _deformation
 from . import rasterizer as _rasterizer
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
+from .rasterizer import FrameOptions, GaussianRasterizationSettings, GaussianRasterizer
 
 # Fused fine stage: deformation and rasterizer behind ONE autograd node, so that the rasterizer backward's per-Gaussian chain rule
 # writes straight into the deformation backward's buffers (fdgs_raster_deform_epilogue) instead of handing five gradient tensors
@@ -102,21 +102,22 @@ def _fill_epilogue(st, b, assign):
     return epi
 
 
-def _fused_backward(states, saved, grad_colors, grad_depths, camera=None, grad_alphas=None, time=None, **prepare):
+def _fused_backward(states, saved, grad_colors, grad_depths, grad_alphas, camera=False, time=False, zero_by_epilogue=False):
     """The backward of the fused fine stage for the views of one autograd node: states = [(deformation state, raster state)], saved = their
     (o_sc, o_rot, o_op) in a row, grad_colors / grad_depths / grad_alphas = the per-view image gradients (or None; alpha: frames rendered
-    with it), `prepare` goes to backward_prepare.
+    with it), `zero_by_epilogue` goes to backward_prepare.
     Last view first (its saved activations, lists and records are the ones still partly resident in the 256 MB Infinity Cache), per view: the
     rasterizer backward, whose epilogue writes into the ONE gradient arena (the first processed view assigns the identity paths, later ones
     accumulate), then that view's deformation backward -- same output pointers and scratch (stream-ordered reuse), its own saved activations.
-    `camera`: a list that receives, per processed view, the 48 floats of fdgs_camera_grad, run behind that view's fdgs_raster_bwd on its
-    accumulator (frames whose camera asks for a gradient: _FusedRenderCameraFunction).  `time`: a list that receives, per processed view, the
-    [1] tensor of fdgs_deform_time_grad, run behind that view's fdgs_deform_bwd (frames whose time asks for one: _FusedRenderTimeFunction)."""
+    `camera`: per view also the 48 floats of fdgs_camera_grad, run behind that view's fdgs_raster_bwd on its accumulator.  `time`: per view
+    also the [1] tensor of fdgs_deform_time_grad, run behind that view's fdgs_deform_bwd.
+    Returns ([d means2D per view], the arena's views in _DeformFunction's input order, [camera rows per view], [time rows per view]); the
+    last two hold None where not asked for."""
     L, stream = _lib.lib(), _lib.stream_ptr()
     st0 = states[0][0]
-    b = _deformation.backward_prepare(st0, saved[0], saved[1], saved[2], identity_assigned=EPILOGUE_ASSIGN, **prepare)
+    b = _deformation.backward_prepare(st0, saved[0], saved[1], saved[2], identity_assigned=EPILOGUE_ASSIGN, zero_by_epilogue=zero_by_epilogue)
     dev = b.d_xyz.device
-    g_means2D, keep = [None] * len(states), []
+    g_means2D, cam_rows, time_rows, keep = [None] * len(states), [None] * len(states), [None] * len(states), []
     for k_, v in enumerate(reversed(range(len(states)))):
         st, rstate = states[v]
         p = rstate.params
@@ -127,126 +128,110 @@ def _fused_backward(states, saved, grad_colors, grad_depths, camera=None, grad_a
         epi = _fill_epilogue(st, b, EPILOGUE_ASSIGN and k_ == 0)
         g, acc = _rasterizer.fill_raster_grads(rstate, gc, gd, gm, epi)      # (acc: zero-filled by the blending forward of this frame, no fill launch here)
         _rasterizer.raster_bwd_call(L, rstate, g, ga)
-        if camera is not None:
-            camera.append(_rasterizer.camera_gradients(rstate, acc))
+        if camera:
+            cam_rows[v] = _rasterizer.camera_gradients(rstate, acc)
         b.g.out_scales, b.g.out_rotations, b.g.out_opacity = _lib.ptr(saved[3 * v]), _lib.ptr(saved[3 * v + 1]), _lib.ptr(saved[3 * v + 2])
         b.g.rot_norm, b.g.saved = _lib.ptr(st.o_norm), _lib.ptr(st.saved_act)
         b.g.packed_rows_ready = epi.tile_flags + 1
         _lib.check(L.fdgs_deform_bwd(stream, st.p, b.g))
         _deformation.note_live_tiles(st, b)
-        if time is not None:
-            time.append(_deformation.time_gradient(st, b))
+        if time:
+            time_rows[v] = _deformation.time_gradient(st, b)
         keep.append((gc, gd, ga, acc, epi))      # (what the queued launches read lives until the last of them is queued)
-    return g_means2D, _deformation.gradient_tuple(st0, b)      # ([d means2D per view], the arena's views in _DeformFunction's input order)
+    return g_means2D, _deformation.gradient_tuple(st0, b), cam_rows, time_rows
 
 
-def _alpha_kw(cfg):
-    """rasterize_forward's keywords of a frame that asked for its alpha image (cfg["alpha"], from pipe.render_alpha) and / or the opacity
-    compensation (cfg["antialiasing"], from pipe.antialiasing); nothing otherwise."""
-    return _rasterizer._frame_kw(cfg.get("alpha"), cfg.get("antialiasing"))
+def _view_forward(cfg, opts, t_scalar, raster_settings, tensors, want, out=None):
+    """One view of the fused fine stage: the deformation at `t_scalar`, then the rasterizer on its outputs -> (deformation state,
+    rasterize_forward's result).  `tensors` = (xyz, scales, rotations, opacity, sh_a, sh_b, aabb, planes..., mlp...); `want`: a backward will
+    follow; `out`: rasterize_forward's.  The one place render(), its nodes and render_views() go through, with the frame's FrameOptions."""
+    st = _deformation.forward_impl(cfg, t_scalar, *tensors[:6], None, tensors[6], tensors[7:], want)
+    res = _rasterizer.rasterize_forward(raster_settings, st.o_xyz, st.o_sh, None, st.o_op, st.o_sc, st.o_rot, None, out=out,
+                                        expect_backward=bool(cfg.get("grad")) and want, **opts.keywords())
+    st.o_xyz = st.o_sh = None
+    return st, res
 
 
-def _wants_alpha(pipe):
-    return bool(getattr(pipe, "render_alpha", False))
+# ---- the autograd nodes of the fused fine stage ----------------------------------------------------------------------------------------------
+# One forward and one backward body (_node_forward, _node_backward); each single-view class is the signature its frames record, around
+# them.  Separate classes, so that a frame whose camera or time does not ask for a gradient records the node, with the inputs, it always
+# recorded -- autograd.Function.apply has a per-input cost (render(): the no-grad branch) -- and makes the C calls it always made.
+
+def _node_forward(ctx, cfg, opts, t_scalar, raster_settings, tensors, want):
+    st, (color, radii, depth, *alpha, rstate) = _view_forward(cfg, opts, t_scalar, raster_settings, tensors, want)
+    ctx.states = [(st, rstate)]
+    ctx.save_for_backward(st.o_sc, st.o_rot, st.o_op)       # (see deformation._node_forward: no reference cycle through ctx)
+    st.o_sc = st.o_rot = st.o_op = None
+    vis = rstate.visibility                                 # radii > 0, written by the projection kernel itself
+    ctx.mark_non_differentiable(radii, vis)
+    ctx.set_materialize_grads(False)
+    return (color, radii, depth, vis, *alpha)               # (alpha: where the frame asked)
 
 
-def _wants_antialiasing(pipe):
-    """Opt-in: every opacity is compensated for the 0.3 px dilation of its footprint (rasterizer.rasterize_forward's antialiasing)."""
-    return bool(getattr(pipe, "antialiasing", False))
+def _node_backward(ctx, image_grads, sink_at, cam_at=None, time_at=None, zero_by_epilogue=False):
+    """One gradient per input of the node.  `image_grads` = the (colour, depth, alpha) gradients, each indexed by view or None.  Where the
+    inputs sit: `sink_at` the gradient sinks of the screen-space means, one per view, with the model's six arrays, the aabb and the network
+    behind them to the end; `cam_at` viewmatrix, projmatrix and campos (ctx.cam), `time_at` the time (ctx.time_like), in the nodes that have
+    them.  Everything in front is no tensor."""
+    out = [None] * len(ctx.needs_input_grad)
+    if all(g is None for g in image_grads):                 # no image reached the loss
+        return tuple(out)
+    camera = cam_at is not None and any(ctx.needs_input_grad[cam_at:cam_at + 3])
+    g_means2D, grads, cam_rows, time_rows = _fused_backward(ctx.states, ctx.saved_tensors, *image_grads, camera=camera, time=time_at is not None,
+                                                            zero_by_epilogue=zero_by_epilogue)
+    model_at = sink_at + len(g_means2D)
+    out[sink_at:model_at] = g_means2D
+    out[model_at:] = grads[:6] + grads[7:]                  # (grads[6]: the deformation's time tensor, no input of these nodes)
+    if camera:
+        out[cam_at:cam_at + 3] = _rasterizer.split_camera_gradients(cam_rows[0], *ctx.cam)
+    if time_at is not None:
+        out[time_at] = _deformation.time_gradient_like(time_rows[0], ctx.time_like)
+    return tuple(out)
+
+
+def _one_view(*image_grads):
+    return [None if g is None else (g,) for g in image_grads]
 
 
 class _FusedRenderFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, cfg, t_scalar, raster_settings, means2D, xyz, scales, rotations, opacity, sh_a, sh_b, aabb, *rest):
-        st = _deformation.forward_impl(cfg, t_scalar, xyz, scales, rotations, opacity, sh_a, sh_b, None, aabb, rest,
-                                       any(ctx.needs_input_grad))
-        color, radii, depth, *alpha, rstate = _rasterizer.rasterize_forward(raster_settings, st.o_xyz, st.o_sh, None, st.o_op, st.o_sc, st.o_rot, None,
-                                                                            expect_backward=bool(cfg.get("grad")) and any(ctx.needs_input_grad),
-                                                                            **_alpha_kw(cfg))
-        ctx.st, ctx.rstate = st, rstate
-        ctx.save_for_backward(st.o_sc, st.o_rot, st.o_op)       # (see _DeformFunction.forward: no reference cycle through ctx)
-        st.o_xyz = st.o_sc = st.o_rot = st.o_op = st.o_sh = None
-        vis = rstate.visibility                                 # radii > 0, written by the projection kernel itself
-        ctx.mark_non_differentiable(radii, vis)
-        ctx.set_materialize_grads(False)
-        return (color, radii, depth, vis, *alpha)               # (alpha: where the frame asked, cfg["alpha"])
+    def forward(ctx, cfg, opts, t_scalar, raster_settings, means2D, *tensors):
+        return _node_forward(ctx, cfg, opts, t_scalar, raster_settings, tensors, any(ctx.needs_input_grad))
 
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_vis=None, grad_alpha=None):
-        st = ctx.st
-        if grad_color is None and grad_depth is None and grad_alpha is None:
-            return (None,) * (11 + len(st.plane_shapes) + len(st.keep[0][8]))
         # one view; the epilogue kernel also clears the accumulate-into part of the arena on the way
-        g_means2D, grads = _fused_backward([(st, ctx.rstate)], ctx.saved_tensors, None if grad_color is None else (grad_color,),
-                                           None if grad_depth is None else (grad_depth,), zero_by_epilogue=EPILOGUE_ASSIGN,
-                                           grad_alphas=None if grad_alpha is None else (grad_alpha,))
-        return (None, None, None, *g_means2D) + grads[:6] + grads[7:]       # (grads[6]: the time tensor, no input here)
+        return _node_backward(ctx, _one_view(grad_color, grad_depth, grad_alpha), sink_at=4, zero_by_epilogue=EPILOGUE_ASSIGN)
 
 
 class _FusedRenderCameraFunction(torch.autograd.Function):
-    """_FusedRenderFunction for a frame whose camera asks for a gradient (rasterizer.camera_wants_grad): viewmatrix, projmatrix and campos of
-    the settings are inputs too and get the gradients of fdgs_camera_grad, run behind the same fdgs_raster_bwd.  A sibling, so that every
-    other frame runs the node and the C calls it always ran."""
+    """The node of a frame whose camera asks for a gradient (rasterizer.camera_wants_grad): viewmatrix, projmatrix and campos of the
+    settings are inputs too and get the gradients of fdgs_camera_grad, run behind the same fdgs_raster_bwd."""
 
     @staticmethod
-    def forward(ctx, cfg, t_scalar, raster_settings, viewmatrix, projmatrix, campos, means2D, xyz, scales, rotations, opacity, sh_a, sh_b, aabb,
-                *rest):
-        st = _deformation.forward_impl(cfg, t_scalar, xyz, scales, rotations, opacity, sh_a, sh_b, None, aabb, rest, True)
-        color, radii, depth, *alpha, rstate = _rasterizer.rasterize_forward(raster_settings, st.o_xyz, st.o_sh, None, st.o_op, st.o_sc, st.o_rot, None,
-                                                                            expect_backward=True, **_alpha_kw(cfg))
-        ctx.st, ctx.rstate, ctx.cam = st, rstate, (viewmatrix, projmatrix, campos)
-        ctx.save_for_backward(st.o_sc, st.o_rot, st.o_op)
-        st.o_xyz = st.o_sc = st.o_rot = st.o_op = st.o_sh = None
-        vis = rstate.visibility
-        ctx.mark_non_differentiable(radii, vis)
-        ctx.set_materialize_grads(False)
-        return (color, radii, depth, vis, *alpha)
+    def forward(ctx, cfg, opts, t_scalar, raster_settings, viewmatrix, projmatrix, campos, means2D, *tensors):
+        ctx.cam = (viewmatrix, projmatrix, campos)
+        return _node_forward(ctx, cfg, opts, t_scalar, raster_settings, tensors, True)
 
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_vis=None, grad_alpha=None):
-        st = ctx.st
-        if grad_color is None and grad_depth is None and grad_alpha is None:
-            return (None,) * (14 + len(st.plane_shapes) + len(st.keep[0][8]))
-        cam = []
-        g_means2D, grads = _fused_backward([(st, ctx.rstate)], ctx.saved_tensors, None if grad_color is None else (grad_color,),
-                                           None if grad_depth is None else (grad_depth,), camera=cam, zero_by_epilogue=EPILOGUE_ASSIGN,
-                                           grad_alphas=None if grad_alpha is None else (grad_alpha,))
-        return (None, None, None, *_rasterizer.split_camera_gradients(cam[0], *ctx.cam), *g_means2D) + grads[:6] + grads[7:]
+        return _node_backward(ctx, _one_view(grad_color, grad_depth, grad_alpha), sink_at=7, cam_at=4, zero_by_epilogue=EPILOGUE_ASSIGN)
 
 
 class _FusedRenderTimeFunction(torch.autograd.Function):
-    """_FusedRenderFunction for a frame whose time asks for a gradient (a scalar tensor that requires grad: fdgs.camera.TimeDelta, tracking
-    a time against a frozen model): the time is an input and gets the [1] result of fdgs_deform_time_grad, run behind the same
-    fdgs_deform_bwd; viewmatrix, projmatrix and campos are inputs too and get fdgs_camera_grad's where one of them asks (joint pose and
-    time).  `t_scalar` is the time's value, read on the host by the caller.  A sibling, so that every other frame runs the node and the C
-    calls it always ran."""
+    """The node of a frame whose time asks for a gradient (a scalar tensor that requires grad: fdgs.camera.TimeDelta, tracking a time against
+    a frozen model): the time is an input and gets the [1] result of fdgs_deform_time_grad, run behind the same fdgs_deform_bwd; viewmatrix,
+    projmatrix and campos are inputs too and get fdgs_camera_grad's where one of them asks (joint pose and time).  `t_scalar` is the time's
+    value, read on the host by the caller."""
 
     @staticmethod
-    def forward(ctx, cfg, t_scalar, raster_settings, time, viewmatrix, projmatrix, campos, means2D, xyz, scales, rotations, opacity, sh_a, sh_b,
-                aabb, *rest):
-        st = _deformation.forward_impl(cfg, t_scalar, xyz, scales, rotations, opacity, sh_a, sh_b, None, aabb, rest, True)
-        color, radii, depth, *alpha, rstate = _rasterizer.rasterize_forward(raster_settings, st.o_xyz, st.o_sh, None, st.o_op, st.o_sc, st.o_rot, None,
-                                                                            expect_backward=True, **_alpha_kw(cfg))
-        ctx.st, ctx.rstate, ctx.cam = st, rstate, (viewmatrix, projmatrix, campos)
-        ctx.time_like, ctx.want_cam = _deformation.time_like(time), any(ctx.needs_input_grad[4:7])
-        ctx.save_for_backward(st.o_sc, st.o_rot, st.o_op)
-        st.o_xyz = st.o_sc = st.o_rot = st.o_op = st.o_sh = None
-        vis = rstate.visibility
-        ctx.mark_non_differentiable(radii, vis)
-        ctx.set_materialize_grads(False)
-        return (color, radii, depth, vis, *alpha)
+    def forward(ctx, cfg, opts, t_scalar, raster_settings, time, viewmatrix, projmatrix, campos, means2D, *tensors):
+        ctx.cam, ctx.time_like = (viewmatrix, projmatrix, campos), _deformation.time_like(time)
+        return _node_forward(ctx, cfg, opts, t_scalar, raster_settings, tensors, True)
 
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_vis=None, grad_alpha=None):
-        st = ctx.st
-        if grad_color is None and grad_depth is None and grad_alpha is None:
-            return (None,) * (15 + len(st.plane_shapes) + len(st.keep[0][8]))
-        cam, tim = ([] if ctx.want_cam else None), []
-        g_means2D, grads = _fused_backward([(st, ctx.rstate)], ctx.saved_tensors, None if grad_color is None else (grad_color,),
-                                           None if grad_depth is None else (grad_depth,), camera=cam, zero_by_epilogue=EPILOGUE_ASSIGN,
-                                           grad_alphas=None if grad_alpha is None else (grad_alpha,), time=tim)
-        d_cam = _rasterizer.split_camera_gradients(cam[0], *ctx.cam) if cam else (None, None, None)
-        return (None, None, None, _deformation.time_gradient_like(tim[0], ctx.time_like), *d_cam, *g_means2D) + grads[:6] + grads[7:]
+        return _node_backward(ctx, _one_view(grad_color, grad_depth, grad_alpha), sink_at=8, cam_at=5, time_at=4, zero_by_epilogue=EPILOGUE_ASSIGN)
 
 
 class _FusedRenderViewsFunction(torch.autograd.Function):
@@ -255,41 +240,31 @@ class _FusedRenderViewsFunction(torch.autograd.Function):
     one arena allocation / zero fill and no per-parameter `grad += grad` kernels (the per-view graph costs 40 of them per extra view)."""
 
     @staticmethod
-    def forward(ctx, cfg, times, settings_list, nviews, *tensors):
-        means2D = tensors[:nviews]
-        xyz, scales, rotations, opacity, sh_a, sh_b, aabb = tensors[nviews:nviews + 7]
-        rest = tensors[nviews + 7:]
+    def forward(ctx, cfg, opts, times, settings_list, nviews, *tensors):
+        tensors = tensors[nviews:]          # (behind the views' gradient sinks: xyz, scales, rotations, opacity, sh_a, sh_b, aabb, network)
         want = any(ctx.needs_input_grad)
-        dev, P = xyz.device, xyz.shape[0]
+        dev, P = tensors[0].device, tensors[0].shape[0]
         H, W = int(settings_list[0].image_height), int(settings_list[0].image_width)
         colors = torch.empty(nviews, 3, H, W, device=dev)          # every view renders straight into its slice
         radii_all = torch.empty(nviews, P, dtype=torch.int32, device=dev)
         depths = torch.empty(nviews, 1, H, W, device=dev)
-        alphas = torch.empty(nviews, 1, H, W, device=dev) if cfg.get("alpha") else None
+        outs = (colors, radii_all, depths) + ((torch.empty(nviews, 1, H, W, device=dev),) if opts.alpha else ())
         states = []
         for v in range(nviews):
-            st = _deformation.forward_impl(cfg, times[v], xyz, scales, rotations, opacity, sh_a, sh_b, None, aabb, rest, want)
-            out = (colors[v], radii_all[v], depths[v]) if alphas is None else (colors[v], radii_all[v], depths[v], alphas[v])
-            *_, rstate = _rasterizer.rasterize_forward(settings_list[v], st.o_xyz, st.o_sh, None, st.o_op, st.o_sc, st.o_rot, None,
-                                                       out=out, expect_backward=bool(cfg.get("grad")) and want, **_alpha_kw(cfg))
-            st.o_xyz = st.o_sh = None
+            st, (*_, rstate) = _view_forward(cfg, opts, times[v], settings_list[v], tensors, want, out=tuple(o[v] for o in outs))
             states.append((st, rstate))
-        ctx.states, ctx.nviews = states, nviews
+        ctx.states = states
         # the activated outputs each view's backward needs: through save_for_backward (no reference cycle through ctx)
         ctx.save_for_backward(*[t for st, _ in states for t in (st.o_sc, st.o_rot, st.o_op)])
         for st, _ in states:
             st.o_sc = st.o_rot = st.o_op = None
         ctx.mark_non_differentiable(radii_all)
         ctx.set_materialize_grads(False)
-        return (colors, radii_all, depths) if alphas is None else (colors, radii_all, depths, alphas)
+        return outs
 
     @staticmethod
     def backward(ctx, grad_colors, grad_radii, grad_depths, grad_alphas=None):
-        st0 = ctx.states[0][0]
-        if grad_colors is None and grad_depths is None and grad_alphas is None:
-            return (None,) * (4 + ctx.nviews + 7 + len(st0.plane_shapes) + len(st0.keep[0][8]))
-        g_means2D, grads = _fused_backward(ctx.states, ctx.saved_tensors, grad_colors, grad_depths, grad_alphas=grad_alphas)
-        return (None, None, None, None, *g_means2D) + grads[:6] + grads[7:]
+        return _node_backward(ctx, (grad_colors, grad_depths, grad_alphas), sink_at=5)
 
 
 def render_views(viewpoint_cameras, pc, pipe, bg_color, scaling_modifier=1.0, stage="fine", cam_type=None):
@@ -309,11 +284,7 @@ def render_views(viewpoint_cameras, pc, pipe, bg_color, scaling_modifier=1.0, st
         return [render(c, pc, pipe, bg_color, scaling_modifier, None, stage, cam_type) for c in cams]
     sinks = [_zero_leaf(means3D) for _ in cams]
     cfg, perm, ins, net_ins = _fine_stage(pc, sinks)       # (the set in Hilbert order for this step where perm is not None)
-    if _wants_alpha(pipe):
-        cfg["alpha"] = True
-    if _wants_antialiasing(pipe):
-        cfg["antialiasing"] = True
-    colors, radii, depths, *alphas = _FusedRenderViewsFunction.apply(cfg, times, settings, len(cams), *ins, *net_ins)
+    colors, radii, depths, *alphas = _FusedRenderViewsFunction.apply(cfg, FrameOptions.of(pipe), times, settings, len(cams), *ins, *net_ins)
     if perm is not None:
         radii = torch.stack(_deformation.permute_rows(perm, [radii[v] for v in range(len(cams))], scatter=True))
     res = [{"render": colors[v], "viewspace_points": sinks[v], "visibility_filter": radii[v] > 0, "radii": radii[v], "depth": depths[v]}
@@ -367,32 +338,26 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     # a leaf's .grad is filled by AccumulateGrad directly (same values, same attribute, read the same way by the train loop)
     screenspace_points = _zero_leaf(means3D)
     raster_settings, frame_time = _frame_settings(viewpoint_camera, cam_type, bg_color, scaling_modifier, pc.active_sh_degree, device, pipe)
-    want_alpha = _wants_alpha(pipe)          # opt-in: "alpha" [1,H,W], the accumulated opacity, joins the result (differentiable)
+    opts = FrameOptions.of(pipe)            # opt-in: "alpha" [1,H,W], the accumulated opacity, joins the result (differentiable); antialiasing
     time_leaf = _time_leaf(viewpoint_camera, cam_type)      # opt-in: the frame time as something to fit (None: every frame there was before)
     if ("fine" in stage and "coarse" not in stage and FUSED_BACKWARD and override_color is None and not pipe.compute_cov3D_python
             and not pipe.convert_SHs_python and isinstance(pc._deformation, _deformation.deform_network)):
         # deformation + rasterizer as one autograd node (see _FusedRenderFunction)
         cfg, perm, ins, net_ins = _fine_stage(pc, (screenspace_points,) if torch.is_grad_enabled() else ())
-        if want_alpha:
-            cfg["alpha"] = True
-        if _wants_antialiasing(pipe):
-            cfg["antialiasing"] = True
         if cfg["grad"] and time_leaf is not None:
             rs = raster_settings
-            rendered_image, radii, depth, vis, *alpha = _FusedRenderTimeFunction.apply(cfg, frame_time, rs, time_leaf, rs.viewmatrix, rs.projmatrix,
-                                                                                       rs.campos, *ins, *net_ins)
+            rendered_image, radii, depth, vis, *alpha = _FusedRenderTimeFunction.apply(cfg, opts, frame_time, rs, time_leaf, rs.viewmatrix,
+                                                                                       rs.projmatrix, rs.campos, *ins, *net_ins)
         elif cfg["grad"] and _rasterizer.camera_wants_grad(raster_settings):
             rs = raster_settings
-            rendered_image, radii, depth, vis, *alpha = _FusedRenderCameraFunction.apply(cfg, frame_time, rs, rs.viewmatrix, rs.projmatrix, rs.campos,
-                                                                                         *ins, *net_ins)
+            rendered_image, radii, depth, vis, *alpha = _FusedRenderCameraFunction.apply(cfg, opts, frame_time, rs, rs.viewmatrix, rs.projmatrix,
+                                                                                         rs.campos, *ins, *net_ins)
         elif cfg["grad"]:
-            rendered_image, radii, depth, vis, *alpha = _FusedRenderFunction.apply(cfg, frame_time, raster_settings, *ins, *net_ins)
+            rendered_image, radii, depth, vis, *alpha = _FusedRenderFunction.apply(cfg, opts, frame_time, raster_settings, *ins, *net_ins)
         else:
             # no graph will be recorded (render.py:57-70, evaluation): the two stages called directly -- autograd.Function.apply costs
             # 0.05 ms per frame for its 46 inputs even when it has nothing to record
-            st = _deformation.forward_impl(cfg, frame_time, *ins, None, net_ins[0], net_ins[1:], False)
-            rendered_image, radii, depth, *alpha, rstate = _rasterizer.rasterize_forward(raster_settings, st.o_xyz, st.o_sh, None, st.o_op, st.o_sc,
-                                                                                         st.o_rot, None, expect_backward=False, **_alpha_kw(cfg))
+            _, (rendered_image, radii, depth, *alpha, rstate) = _view_forward(cfg, opts, frame_time, raster_settings, (*ins, *net_ins), False)
             vis = rstate.visibility
         if perm is not None:       # (radii and visibility back in the model's own row order)
             radii, = _deformation.permute_rows(perm, [radii], scatter=True)
@@ -447,8 +412,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         colors_precomp = override_color
         shs_final = None
 
-    rasterizer = GaussianRasterizer(raster_settings=raster_settings, render_alpha=want_alpha)       # (an nn.Module: only built on the paths that call it)
-    if _wants_antialiasing(pipe):
+    rasterizer = GaussianRasterizer(raster_settings=raster_settings, render_alpha=opts.alpha)       # (an nn.Module: only built on the paths that call it)
+    if opts.antialiasing:
         rasterizer.antialiasing = True
     rendered_image, radii, depth, *alpha = rasterizer(
         means3D=means3D_final, means2D=means2D, shs=shs_final, colors_precomp=colors_precomp, opacities=opacity_final,
