@@ -151,6 +151,9 @@ SYMBOLS = {
     "fdgs_preprocess_host_aa": (c_int, [POINTER(RasterParams)] + [c_void_p] * 10),
     "fdgs_preprocess_bwd_host_aa": (c_int, [POINTER(RasterParams)] + [c_void_p] * 15),
     "fdgs_camera_grad_host_aa": (c_int, [POINTER(RasterParams)] + [c_void_p] * 9),
+    # ... with the absolute screen-space sums: raster_bwd_alpha / raster_bwd_aa (the int picks) and one more [P,3] output (NULL: those calls)
+    "fdgs_raster_bwd_abs": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_uint32, POINTER(RasterGrads), c_void_p,
+                                    c_int, c_void_p]),
     "fdgs_mark_visible": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdgs_preprocess_host": (c_int, [POINTER(RasterParams)] + [c_void_p] * 9),
     "fdgs_preprocess_bwd_host": (c_int, [POINTER(RasterParams)] + [c_void_p] * 13),

@@ -193,6 +193,8 @@ struct PreBwdArgs : FrameHead {
     // EPI: the deformation epilogue (fdgs_raster_deform_epilogue) + the activated opacities the rasterizer received
     fdgs_raster_deform_epilogue epi;
     const float* opacities;
+    float* dL_dmeans2D_abs;      // ABSROW [P,3] (fdgs_raster_bwd_abs): slots 10, 11 of the line in NDC units and a zero.  (Last: the offsets
+                                 // of the fields above are the ones the instantiations without it have always read.)
 };
 
 // Block-linear store of K floats per Gaussian for the 64 Gaussians of a wave: lanes park their K values in LDS as
@@ -232,7 +234,9 @@ __device__ __forceinline__ void wave_store_rows(float* __restrict__ out_block, c
 // (this is deform_bwd_prep_kernel's job done where the values are still in registers: one kernel and 2 x 236 B per Gaussian less).
 // AA (the state was projected by preprocess_fwd_kernel<*, true>): the opacity sum of the accumulator line is g = dL/d(opacity * h), so
 // dL/dopacity = h * g and g * opacity enters the covariance's gradient through h (gs_math.h aa_bwd); any_grad already covers the word.
-template <bool EPI, bool AA>
+// ABSROW (fdgs_raster_bwd_abs): every row also writes its absolute screen-space row; a frame that does not ask runs the instantiations, and
+// the instructions, it always ran.
+template <bool EPI, bool AA, bool ABSROW = false>
 __global__ void __launch_bounds__(256) preprocess_bwd_kernel(PreBwdArgs a) {
     __shared__ __attribute__((aligned(16))) float lds_all[4 * 64 * (EPI ? 64 : 48)];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -291,6 +295,14 @@ __global__ void __launch_bounds__(256) preprocess_bwd_kernel(PreBwdArgs a) {
         g0 = ga[0]; g1 = ga[1]; g2 = ga[2];
         any_grad = g0.x != 0.f || g0.y != 0.f || g0.z != 0.f || g0.w != 0.f || g1.x != 0.f || g1.y != 0.f || g1.z != 0.f || g1.w != 0.f ||
                    g2.x != 0.f || g2.y != 0.f;
+    }
+    // The absolute screen-space sums (slots 10, 11: written by the ABS blending backward): a row of its own, block-linear, stored before the
+    // chain rule so that nothing of it is live across that.  Whether or not any_grad holds: a signed line can be all zeros while the absolute
+    // sums are not.  Culled rows and rows no pixel blended write the zeros they were initialised / filled with.
+    if constexpr (ABSROW) {
+        float ab[3] = {0.f, 0.f, 0.f};
+        if (active) mean2d_grad_to_ndc(g2.z, g2.w, a.W, a.H, ab);
+        wave_store_rows<3>(a.dL_dmeans2D_abs + (size_t)n0 * 3, ab, nvalid, buf, lane);
     }
     if (active && any_grad) {
         CamConst c;
@@ -680,7 +692,7 @@ extern "C" int fdgs_preprocess_fwd_aa(void* stream_, const fdgs_raster_params* p
 
 // called from fdgs_raster_bwd (render.hip)
 int fdgs_launch_preprocess_bwd(hipStream_t stream, const fdgs_raster_params* p, const void* geom,
-                               const fdgs_raster_grads* g, bool antialiasing) {
+                               const fdgs_raster_grads* g, bool antialiasing, float* means2D_abs) {
     if (p->P == 0) return FDGS_OK;
     FDGS_REQUIRE(!antialiasing || p->opacities, "opacities is NULL (an antialiased frame's backward reads them)");
     GeomLayout gl = geom_layout(p->P);
@@ -692,6 +704,7 @@ int fdgs_launch_preprocess_bwd(hipStream_t stream, const fdgs_raster_params* p, 
     a.dL_dcolors = g->dL_dcolors; a.dL_dmeans3D = g->dL_dmeans3D; a.dL_dsh = g->dL_dsh; a.dL_dscales = g->dL_dscales;
     a.dL_drot = g->dL_drotations; a.dL_dcov3D = g->dL_dcov3D;
     a.opacities = p->opacities;
+    a.dL_dmeans2D_abs = means2D_abs;
     const fdgs_raster_deform_epilogue* e = g->deform_epilogue;
     if (e) {
         FDGS_REQUIRE(p->shs && p->sh_coeffs == 16 && p->scales && p->rotations && !p->cov3D_precomp,
@@ -703,8 +716,13 @@ int fdgs_launch_preprocess_bwd(hipStream_t stream, const fdgs_raster_params* p, 
     }
     {
         FDGS_TIMED("preprocess_bwd", stream);
-        void (*const epi)(PreBwdArgs) = antialiasing ? preprocess_bwd_kernel<true, true> : preprocess_bwd_kernel<true, false>;
-        void (*const plain)(PreBwdArgs) = antialiasing ? preprocess_bwd_kernel<false, true> : preprocess_bwd_kernel<false, false>;
+        using Kernel = void (*)(PreBwdArgs);
+        Kernel epi = antialiasing ? preprocess_bwd_kernel<true, true> : preprocess_bwd_kernel<true, false>;
+        Kernel plain = antialiasing ? preprocess_bwd_kernel<false, true> : preprocess_bwd_kernel<false, false>;
+        if (means2D_abs) {
+            epi = antialiasing ? preprocess_bwd_kernel<true, true, true> : preprocess_bwd_kernel<true, false, true>;
+            plain = antialiasing ? preprocess_bwd_kernel<false, true, true> : preprocess_bwd_kernel<false, false, true>;
+        }
         if (e) hipLaunchKernelGGL(epi, dim3(cdiv(e->Npad, 256)), dim3(256), 0, stream, a);
         else hipLaunchKernelGGL(plain, dim3(cdiv(p->P, 256)), dim3(256), 0, stream, a);
     }

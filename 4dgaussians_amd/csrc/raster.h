@@ -29,8 +29,9 @@ int render_fwd_impl(void* stream_, const fdgs_raster_params* p, const void* geom
 // the projection launchers (preprocess.hip).  host_count_dev (capacity mode): device address of the pinned host word that receives the
 // pair count from the kernel's last workgroup.  count_tiles (one-call frame, counts_in_projection): the kernel also counts the pairs of
 // every tile into geom's tile_counts, cleared by the same fill as the header in front of them.  antialiasing (the *_aa entry points): the
-// projection writes opacity * h into recB.y, and the backward of such a state carries h's chain rule (gs_math.h aa_comp / aa_bwd)
+// projection writes opacity * h into recB.y, and the backward of such a state carries h's chain rule (gs_math.h aa_comp / aa_bwd).
+// means2D_abs (fdgs_raster_bwd_abs): opt [P,3], the absolute screen-space sums of the accumulator line, one row per Gaussian
 int fdgs_preprocess_fwd_impl(void* stream_, const fdgs_raster_params* p, void* geom, int32_t* radii, uint32_t* host_count_dev,
                              bool count_tiles = false, bool antialiasing = false);
 int fdgs_launch_preprocess_bwd(hipStream_t stream, const fdgs_raster_params* p, const void* geom, const fdgs_raster_grads* g,
-                               bool antialiasing = false);
+                               bool antialiasing = false, float* means2D_abs = nullptr);

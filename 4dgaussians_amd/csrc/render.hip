@@ -7,7 +7,9 @@
 // reduce-scatter and issues ONE 64-byte atomic line-op per (tile, Gaussian) into a packed [P,16] gradient array.  The 256-thread
 // backward of rounds 1-2 (four waves meeting in LDS slots) stays selectable (tuning knob rbwd_ppl = 0; 2 = two waves per tile with two
 // pixels per lane): the three forms are compared with each other in tests/test_gpu_raster.py.  (A strip form of the FORWARD measured
-// slower and was dropped in round 3.)
+// slower and was dropped in round 3.)  All three forms have an ABS instantiation (fdgs_raster_bwd_abs): beside the signed sums it adds, per
+// Gaussian, the ABSOLUTE values of every pixel's screen-space gradient (the densification statistic of AbsGS) into slots 10 and 11 of the same
+// line, with the same reductions and the same atomic; a frame that does not ask launches the instantiations it always launched.
 // Pick pass (render_pick_kernel): the forward's layout once more over a finished frame's lists, for the id of the Gaussian with the largest
 // blend weight and the id and depth of the one at which the accumulated alpha reaches a cut; it writes nothing into the frame.
 // Contribution pass (render_contrib_kernel): that walk again, reduced per Gaussian instead of per pixel -- the sum and the maximum of the
@@ -674,6 +676,25 @@ __device__ __forceinline__ float wave_reduce_scatter10(float a0, float a1, float
     return __uint_as_float(q[0]) + __uint_as_float(q[1]);                      // lower half: e01 totals, upper half: e2 totals
 }
 
+// ... and of twelve (the blending backward with the absolute screen-space sums, values 10 and 11): the third group of four is whole, so it
+// goes through both butterflies like the two others and the upper half-wave ends with sum(a[8 + (lane & 3)]).
+__device__ __forceinline__ float wave_reduce_scatter12(float a0, float a1, float a2, float a3, float a4, float a5, float a6, float a7,
+                                                       float a8, float a9, float a10, float a11, int lane) {
+    const bool b0 = lane & 1, b1 = lane & 2;
+    auto rs1 = [&](float lo, float hi) { const float keep = b0 ? hi : lo, send = b0 ? lo : hi; return keep + dpp_f<0xB1>(send); };   // lane ^ 1
+    auto rs2 = [&](float lo, float hi) { const float keep = b1 ? hi : lo, send = b1 ? lo : hi; return keep + dpp_f<0x4E>(send); };   // lane ^ 2
+    const float c0 = rs1(a0, a1), c1 = rs1(a2, a3), c2 = rs1(a4, a5), c3 = rs1(a6, a7), c4 = rs1(a8, a9), c5 = rs1(a10, a11);
+    float d0 = rs2(c0, c1), d1 = rs2(c2, c3), d2 = rs2(c4, c5);
+    d0 += dpp_f<0x124>(d0); d1 += dpp_f<0x124>(d1); d2 += dpp_f<0x124>(d2);     // row_ror:4
+    d0 += dpp_f<0x128>(d0); d1 += dpp_f<0x128>(d1); d2 += dpp_f<0x128>(d2);     // row_ror:8
+    auto q01 = __builtin_amdgcn_permlane16_swap(__float_as_uint(d0), __float_as_uint(d1), false, false);
+    const float e01 = __uint_as_float(q01[0]) + __uint_as_float(q01[1]);
+    auto q2 = __builtin_amdgcn_permlane16_swap(__float_as_uint(d2), __float_as_uint(d2), false, false);
+    const float e2 = __uint_as_float(q2[0]) + __uint_as_float(q2[1]);
+    auto q = __builtin_amdgcn_permlane32_swap(__float_as_uint(e01), __float_as_uint(e2), false, false);
+    return __uint_as_float(q[0]) + __uint_as_float(q[1]);
+}
+
 struct RenderBwdArgs : BlendHead {
     const uint2* ranges; const uint32_t* pair_gid;
     const float4 *recA, *recB, *recC;
@@ -682,7 +703,11 @@ struct RenderBwdArgs : BlendHead {
     const float *dL_dcolor, *dL_ddepth;
     const float* dL_dalpha;                  // opt [H*W]: gradient of the accumulated opacity A = 1 - final_T (fdgs_raster_bwd_alpha)
     float* gacc;  // [P,16] per-Gaussian gradient line: 0,1 mean2D (pixel units) | 2,3,4 conic xx,xy(half),yy | 5 opacity |
-                  // 6,7,8 rgb | 9 depth | 10..15 unused.  One 64-B line per Gaussian => one atomic line-op per (tile,Gaussian)
+                  // 6,7,8 rgb | 9 depth | 10,11 sums over the pixels of |d L_pixel / d mean2D| (x, y; pixel units), written by the ABS
+                  // instantiations only | 12..15 unused.  One 64-B line per Gaussian => one atomic line-op per (tile,Gaussian).
+                  // All 16 floats of every line are zero when the kernel starts, whoever filled them: the forward's fill (RenderArgs::zfill,
+                  // P * 4 float4) and the backward's own (raster_bwd_impl, P * 64 bytes) both cover the whole line, so slots 10..15 of a
+                  // frame that does not ask stay zero and an ABS kernel adds into zeros.
 };
 
 // DEPTH: a gradient w.r.t. the depth image was handed in (dL_ddepth != NULL).  The reference's training loss never uses it
@@ -693,11 +718,13 @@ struct RenderBwdArgs : BlendHead {
 // permlane16/32 swaps across the rows on the ONE value each lane carries) and lanes 0..NV-1 store it with a plain ds_write; the flush
 // adds the four slots.  (Until round 3 the rows met in LDS float atomics on one shared slot -- ds_add_f32 sustains 0.33 lanes/clk/CU,
 // profiles/r01_lds_atomic_microbench.txt, and rocprofv3 showed the waves waiting 39 % of their cycles.)
-template <bool DEPTH, int ROUND>
+// ABS: the absolute screen-space sums as well (fdgs_raster_bwd_abs): |g_mx| and |g_my| of every pixel are values 10 and 11 of the same
+// reductions, slots and flush (NV = 12 whatever DEPTH is, so that value k stays slot k of the line; the depth value is then a zero).
+template <bool DEPTH, int ROUND, bool ABS = false>
 __global__ void __launch_bounds__(256) render_bwd_kernel(RenderBwdArgs a) {
     const int tile = unit_lookup(a.order, a.per_xcd, blockIdx.x, a.gx, a.gy, 1, a.bh);
     if (tile < 0) return;
-    constexpr int NV = DEPTH ? 10 : 9;
+    constexpr int NV = ABS ? 12 : DEPTH ? 10 : 9;
     __shared__ float4 sA[ROUND], sB[ROUND], sC[ROUND];
     __shared__ uint32_t sGid[ROUND];
     __shared__ float sAcc[ROUND * 4 * NV];
@@ -791,6 +818,8 @@ __global__ void __launch_bounds__(256) render_bwd_kernel(RenderBwdArgs a) {
             }
             // per-Gaussian sums over the wave's 64 pixels: DPP butterflies inside each 16-lane row (4 instructions per value); lane
             // `sub` of every row then picks value `sub` and the four rows are added with two permlane swaps on that ONE value
+            [[maybe_unused]] float g_ax, g_ay;       // (ABS) this pixel's |g_mx|, |g_my| (an invalid pixel: |0|), summed like the others
+            if constexpr (ABS) { g_ax = row_allsum(fabsf(g_mx)); g_ay = row_allsum(fabsf(g_my)); }
             g_mx = row_allsum(g_mx); g_my = row_allsum(g_my);
             g_cxx = row_allsum(g_cxx); g_cxy = row_allsum(g_cxy); g_cyy = row_allsum(g_cyy);
             g_op = row_allsum(g_op);
@@ -801,6 +830,7 @@ __global__ void __launch_bounds__(256) render_bwd_kernel(RenderBwdArgs a) {
             v = sub == 1 ? g_my : v; v = sub == 2 ? g_cxx : v; v = sub == 3 ? g_cxy : v; v = sub == 4 ? g_cyy : v;
             v = sub == 5 ? g_op : v; v = sub == 6 ? g_c0 : v; v = sub == 7 ? g_c1 : v; v = sub == 8 ? g_c2 : v;
             if (DEPTH) v = sub == 9 ? g_d : v;
+            if constexpr (ABS) { v = (!DEPTH && sub == 9) ? 0.f : v; v = sub == 10 ? g_ax : v; v = sub == 11 ? g_ay : v; }
             {
                 auto q = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
                 v = __uint_as_float(q[0]) + __uint_as_float(q[1]);
@@ -849,7 +879,11 @@ __device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elem
 __device__ __forceinline__ v2f splat2(float x) { return v2f{x, x}; }
 
 // PPL = 2 * NP pixels per lane, held as NP float2 pairs so that the per-pixel arithmetic issues as v_pk_{mul,add,fma}_f32
-template <bool DEPTH, int NP>
+// ABS: the absolute screen-space sums as well (fdgs_raster_bwd_abs).  The moments cannot give them -- the sign of a pixel's term depends on
+// dy --, so a lane forms per pixel hx = cxx dx + cxy dy and hy = cyy dy + cxy dx (the pixel's d power / d mean, sign turned) on the pairs it
+// holds and adds |v| |hx| and |v| |hy|; |opacity| is applied once per lane.  The two lane sums are values 10 and 11 of a twelve-value
+// reduce-scatter and land in slots 10 and 11 of the line with the same atomic instruction.
+template <bool DEPTH, int NP, bool ABS = false>
 __global__ void __launch_bounds__(64) render_bwd_strip_kernel(RenderBwdArgs a) {
     constexpr int PPL = 2 * NP;
     constexpr int PARTS = 4 / PPL;
@@ -864,8 +898,9 @@ __global__ void __launch_bounds__(64) render_bwd_strip_kernel(RenderBwdArgs a) {
     const float pxf = (float)x;
     const size_t hw = (size_t)a.H * a.W;
     // which of the per-Gaussian sums this lane holds after wave_reduce_scatter10, and whether it is the lane that sends it
-    const int slot = lane < 16 ? (lane & 3) : lane < 32 ? 4 + (lane & 3) : 8 + (lane & 1);
-    const bool slot_on = (lane & 15) < 4 && (lane < 32 || (lane < 48 && (lane & 15) < (DEPTH ? 2 : 1)));
+    // (ABS, wave_reduce_scatter12: the upper half-wave holds 8 + (lane & 3); lanes 34 and 35 send the absolute sums, lane 33 the depth's)
+    const int slot = lane < 16 ? (lane & 3) : lane < 32 ? 4 + (lane & 3) : 8 + (lane & (ABS ? 3 : 1));
+    const bool slot_on = (lane & 15) < 4 && (lane < 32 || (lane < 48 && ((lane & 15) < (DEPTH ? 2 : 1) || (ABS && (lane & 15) >= 2))));
     const uint2 range = a.ranges[tile];
     v2f py[NP], T[NP], tfb[NP], dp0[NP], dp1[NP], dp2[NP], ddep[NP], acc0[NP], acc1[NP], acc2[NP], accd[NP];
     v2f dal[NP];                         // dL/dA of the pixels (0 without a.dL_dalpha): only lives until tfb is formed
@@ -946,6 +981,8 @@ __global__ void __launch_bounds__(64) render_bwd_strip_kernel(RenderBwdArgs a) {
             if (!__any(any)) continue;
             const float4 Cc = sC[j];
             v2f V0 = splat2(0.f), V1 = V0, V2 = V0, gc0 = V0, gc1 = V0, gc2 = V0, gd = V0;
+            [[maybe_unused]] v2f Ax = V0, Ay = V0;       // (ABS) sums of |v| |hx|, |v| |hy| over the lane's pixels
+            [[maybe_unused]] const float cxdx = A.z * dx, cydx = A.w * dx;
 #pragma unroll
             for (int p = 0; p < NP; p++) {
                 v2f al;
@@ -974,6 +1011,11 @@ __global__ void __launch_bounds__(64) render_bwd_strip_kernel(RenderBwdArgs a) {
                 v[1] = valid[2 * p + 1] ? v[1] : 0.f;
                 const v2f vy = v * dy[p];
                 V0 += v; V1 += vy; V2 = fma2(vy, dy[p], V2);
+                if constexpr (ABS) {
+                    const v2f hx = fma2(splat2(A.w), dy[p], splat2(cxdx)), hy = fma2(splat2(B.x), dy[p], splat2(cydx));
+                    const v2f av = __builtin_elementwise_abs(v);
+                    Ax = fma2(av, __builtin_elementwise_abs(hx), Ax); Ay = fma2(av, __builtin_elementwise_abs(hy), Ay);
+                }
             }
             // the lane's six geometric sums from its moments over dy (dL_dG * G = opacity * v)
             const float u0 = B.y * (V0[0] + V0[1]), u1 = B.y * (V1[0] + V1[1]), u2 = B.y * (V2[0] + V2[1]);
@@ -984,7 +1026,13 @@ __global__ void __launch_bounds__(64) render_bwd_strip_kernel(RenderBwdArgs a) {
             float g_c0 = gc0[0] + gc0[1], g_c1 = gc1[0] + gc1[1], g_c2 = gc2[0] + gc2[1], g_d = gd[0] + gd[1];
             // nine (ten) sums over the wave's 64 lanes as a reduce-scatter: each butterfly step halves the number of values a lane
             // carries (36 instructions instead of 50 for nine all-reduces + select); lane `slot_lane` ends with value `slot`
-            const float v = wave_reduce_scatter10<DEPTH>(g_mx, g_my, g_cxx, g_cxy, g_cyy, g_op, g_c0, g_c1, g_c2, g_d, lane);
+            float v;
+            if constexpr (ABS) {
+                const float aop = fabsf(B.y);
+                v = wave_reduce_scatter12(g_mx, g_my, g_cxx, g_cxy, g_cyy, g_op, g_c0, g_c1, g_c2, g_d, aop * (Ax[0] + Ax[1]), aop * (Ay[0] + Ay[1]), lane);
+            } else {
+                v = wave_reduce_scatter10<DEPTH>(g_mx, g_my, g_cxx, g_cxy, g_cyy, g_op, g_c0, g_c1, g_c2, g_d, lane);
+            }
             if (slot_on && v != 0.f) atomicAdd(&a.gacc[(size_t)sGid[j] * 16 + slot], v);
         }
     }
@@ -1056,14 +1104,19 @@ static void fill_replay_args(ReplayArgs& a, const fdgs_raster_params* p, const v
 
 // The blending backward's form.  ppl = pixels per lane of the strip form (one wave per workgroup, 4 / ppl of them per tile); anything but
 // 2 or 4 = the 256-thread form (128 entries staged per round keeps six workgroups per CU at 25 KB of LDS each).  depth: dL_ddepth was
-// handed in.  (The tables name the instantiations in the order the device code has always listed them.)
-static void launch_render_bwd(hipStream_t stream, int ppl, bool depth, const RenderBwdArgs& a) {
+// handed in.  abs: the absolute screen-space sums too (slots 10, 11); a frame without them launches the instantiations it always launched.
+// (The tables name the instantiations in the order the device code has always listed them.)
+static void launch_render_bwd(hipStream_t stream, int ppl, bool depth, bool abs, const RenderBwdArgs& a) {
     using Kernel = void (*)(RenderBwdArgs);
     static const Kernel strip[2][2] = {{render_bwd_strip_kernel<true, 1>, render_bwd_strip_kernel<true, 2>},
                                        {render_bwd_strip_kernel<false, 1>, render_bwd_strip_kernel<false, 2>}};
     static const Kernel whole[2] = {render_bwd_kernel<true, 128>, render_bwd_kernel<false, 128>};
-    if (ppl == 2 || ppl == 4) hipLaunchKernelGGL(strip[depth ? 0 : 1][ppl / 4], dim3(unit_grid(a.gx, a.gy, 4 / ppl, a.bh)), dim3(64), 0, stream, a);
-    else hipLaunchKernelGGL(whole[depth ? 0 : 1], dim3(unit_grid(a.gx, a.gy, 1, a.bh)), dim3(256), 0, stream, a);
+    static const Kernel strip_abs[2][2] = {{render_bwd_strip_kernel<true, 1, true>, render_bwd_strip_kernel<true, 2, true>},
+                                           {render_bwd_strip_kernel<false, 1, true>, render_bwd_strip_kernel<false, 2, true>}};
+    static const Kernel whole_abs[2] = {render_bwd_kernel<true, 128, true>, render_bwd_kernel<false, 128, true>};
+    if (ppl == 2 || ppl == 4)
+        hipLaunchKernelGGL((abs ? strip_abs : strip)[depth ? 0 : 1][ppl / 4], dim3(unit_grid(a.gx, a.gy, 4 / ppl, a.bh)), dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL((abs ? whole_abs : whole)[depth ? 0 : 1], dim3(unit_grid(a.gx, a.gy, 1, a.bh)), dim3(256), 0, stream, a);
 }
 
 }  // namespace fdgs
@@ -1196,12 +1249,15 @@ extern "C" int fdgs_render_contrib(void* stream_, const fdgs_raster_params* p, c
 
 // fdgs_raster_bwd (dL_dalpha == nullptr), fdgs_raster_bwd_alpha and fdgs_raster_bwd_aa (antialiasing: the blending backward is the same --
 // its opacity sum is then the gradient of the compensated opacity -- and the per-Gaussian chain rule carries the compensation's)
+// ... and fdgs_raster_bwd_abs (means2D_abs [P,3], opt: the blending backward also sums the absolute screen-space terms, slots 10 and 11 of
+// the line, and the chain rule writes them out; a row no pixel blended reads the zeros the line was filled with)
 static int raster_bwd_impl(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img, uint32_t R,
-                           const fdgs_raster_grads* g, const float* dL_dalpha, bool antialiasing = false) {
+                           const fdgs_raster_grads* g, const float* dL_dalpha, bool antialiasing = false, float* means2D_abs = nullptr) {
     int rc = validate_raster_params(p);
     if (rc) return rc;
     FDGS_REQUIRE(g && geom && img && (binning || R == 0), "NULL buffer");
     FDGS_REQUIRE(aligned_to(dL_dalpha, 4), "dL_dalpha must be 4-byte aligned");
+    FDGS_REQUIRE(aligned_to(means2D_abs, 4), "dL_dmeans2D_abs must be 4-byte aligned");
     if (p->P == 0) return FDGS_OK;      // an empty set: no row to write (its optional per-row inputs may come without their gradient buffers)
     if (g->deform_epilogue) {     // the per-Gaussian results go to the deformation backward's buffers instead (include/fdgs.h)
         FDGS_REQUIRE(g->dL_dcolor && g->dL_dmeans2D && g->scratch_acc, "required gradient buffer is NULL");
@@ -1232,11 +1288,12 @@ static int raster_bwd_impl(void* stream_, const fdgs_raster_params* p, const voi
             // -1 (default): by image size -- one wave per tile leaves the chip underfilled when the image has fewer tiles than the chip has wave
             // slots (1 024 SIMDs x 4): two waves per tile then (config 3, 2 040 tiles: blending backward 0.274 -> 0.213 ms; config 2, 2 500
             // tiles: 0.197 -> 0.187; at 5 440 tiles four pixels per lane win by 10 %, profiles/r05_rbwd_ppl_small_images_ab.txt)
-            launch_render_bwd(stream, g_tune.rbwd_ppl >= 0 ? g_tune.rbwd_ppl : (a.gx * a.gy <= 4096 ? 2 : 4), g->dL_ddepth != nullptr, a);
+            launch_render_bwd(stream, g_tune.rbwd_ppl >= 0 ? g_tune.rbwd_ppl : (a.gx * a.gy <= 4096 ? 2 : 4), g->dL_ddepth != nullptr,
+                              means2D_abs != nullptr, a);
         }
         FDGS_LAUNCH_CHECK("render_bwd", p->debug, stream);
     }
-    return fdgs_launch_preprocess_bwd(stream, p, geom, g, antialiasing);
+    return fdgs_launch_preprocess_bwd(stream, p, geom, g, antialiasing, means2D_abs);
 }
 
 extern "C" int fdgs_raster_bwd(void* stream_,const fdgs_raster_params* p, const void* geom, const void* binning,
@@ -1252,4 +1309,9 @@ extern "C" int fdgs_raster_bwd_alpha(void* stream_, const fdgs_raster_params* p,
 extern "C" int fdgs_raster_bwd_aa(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning,
                                   const void* img, uint32_t R, const fdgs_raster_grads* g, const float* dL_dalpha) {
     return raster_bwd_impl(stream_, p, geom, binning, img, R, g, dL_dalpha, true);
+}
+
+extern "C" int fdgs_raster_bwd_abs(void* stream_, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
+                                   uint32_t R, const fdgs_raster_grads* g, const float* dL_dalpha, int antialiased, float* dL_dmeans2D_abs) {
+    return raster_bwd_impl(stream_, p, geom, binning, img, R, g, dL_dalpha, antialiased != 0, dL_dmeans2D_abs);
 }

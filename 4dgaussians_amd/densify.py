@@ -49,7 +49,10 @@ def _f32(t):
 
 def add_densification_stats(pc, viewspace_point_tensor, update_filter, radii=None):
     """xyz_gradient_accum[f] += |grad[f, :2]|, denom[f] += 1 (scene/gaussian_model.py:516-518) and, when `radii` is given,
-    max_radii2D[f] = max(max_radii2D[f], radii[f]) (train.py:261), in place, without the host syncs of boolean indexing."""
+    max_radii2D[f] = max(max_radii2D[f], radii[f]) (train.py:261), in place, without the host syncs of boolean indexing.
+    Any [P, >= 2] tensor is taken: passing `viewspace_points.absgrad` of a frame rendered with `pipe.absgrad = True` instead of `.grad`
+    accumulates the absolute screen-space gradients (AbsGS) -- that is the whole switch.  The statistic is larger than the signed one, so
+    AbsGS raises the clone / split threshold; that number is the caller's."""
     g = viewspace_point_tensor          # (the reference passes the GRADIENT tensor under this name, train.py:262)
     if g.device.type != "cuda":
         raise _lib.FdgsError("the densification kernels run on the GPU only")

@@ -414,7 +414,8 @@ def allreduce_gradients(params, bucket_bytes=512 << 20, average=False, arena_zer
 
 def allreduce_densification_stats(radii, visibility_filter, viewspace_grad):
     """Cross-rank form of what train.py:195-196,219-225 does over the views of one step: element-wise MAX of the radii,
-    OR of the visibility masks, SUM of the view-space position gradients.  Returns the three reduced tensors."""
+    OR of the visibility masks, SUM of the view-space position gradients.  Returns the three reduced tensors.
+    `viewspace_grad` may as well be `viewspace_points.absgrad` (pipe.absgrad): the sum over the ranks of the absolute gradients."""
     if not (dist.is_initialized() and dist.get_world_size() > 1):
         return radii, visibility_filter, viewspace_grad
     r = radii.clone()

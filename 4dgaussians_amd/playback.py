@@ -197,7 +197,7 @@ def _state_frame(st, raster_settings, to_stored, to_model, override_color, rgb8,
         shs, colors = None, override_color.detach().float()
         if to_stored is not None:
             colors = to_stored(colors)
-    opts = _rasterizer.FrameOptions.of(pipe)._replace(alpha=False)       # (a playback frame takes the projection's option only)
+    opts = _rasterizer.FrameOptions.of(pipe)._replace(alpha=False, absgrad=False)       # (a playback frame takes the projection's option only)
     image, radii, depth, rstate = _rasterizer.rasterize_forward(raster_settings, st.xyz, shs, colors, st.opacity, st.scales, st.rotations,
                                                                 None, expect_backward=False, **opts.keywords())
     vis = rstate.visibility

@@ -50,20 +50,23 @@ class GaussianRasterizationSettings(NamedTuple):
 class FrameOptions(NamedTuple):
     """What a frame asks of the rasterizer beyond colour, radii and depth; all off: the frame the reference renders.  `alpha`: the frame also
     delivers its accumulated opacity 1 - final_T.  `antialiasing`: the projection compensates every opacity for the 0.3 px dilation of its
-    footprint.  Built once per frame and handed on as itself; which C entry point each stage then calls: _stage_call."""
+    footprint.  `absgrad`: the frame's backward also returns the absolute screen-space gradients (include/fdgs.h at fdgs_raster_bwd_abs) and
+    leaves them on the gradient sink of the screen-space means as its attribute `.absgrad`.  Built once per frame and handed on as itself;
+    which C entry point each stage then calls: _stage_call."""
     alpha: bool = False
     antialiasing: bool = False
+    absgrad: bool = False
 
     @classmethod
     def of(cls, source):
-        """The options `source` asks for through its attributes `render_alpha` and `antialiasing`: the `pipe` of render() (absent: off), a
-        GaussianRasterizer."""
-        return cls(bool(getattr(source, "render_alpha", False)), bool(getattr(source, "antialiasing", False)))
+        """The options `source` asks for through its attributes `render_alpha`, `antialiasing` and `absgrad`: the `pipe` of render() (absent:
+        off), a GaussianRasterizer."""
+        return cls(bool(getattr(source, "render_alpha", False)), bool(getattr(source, "antialiasing", False)), bool(getattr(source, "absgrad", False)))
 
     def keywords(self):
         """rasterize_forward's keywords for what the frame asked.  A frame that asked for nothing passes none: its call is the one that
         function, and whatever a test puts in its place, has always received."""
-        return {k: True for k, v in (("want_alpha", self.alpha), ("antialiasing", self.antialiasing)) if v}
+        return {k: True for k, v in (("want_alpha", self.alpha), ("antialiasing", self.antialiasing), ("absgrad", self.absgrad)) if v}
 
 
 PLAIN = FrameOptions()
@@ -74,13 +77,18 @@ PLAIN = FrameOptions()
 #   neither     -> the plain form, without the argument.
 # The projection and the camera gradient have no alpha image, hence no _alpha form and no such argument; the blend has no _aa form: the
 # projection carries the compensation, an antialiased frame blends like any other.
+# The backward of a frame that asked for the absolute screen-space gradients has ONE form, fdgs_raster_bwd_abs, whatever else the frame asked:
+# it takes the alpha gradient (or NULL), the antialiasing case as an int and the [P,3] output.
 _STAGE_FORMS = {"preprocess_fwd": ("_aa",), "raster_fwd_capacity": ("_aa", "_alpha"), "render_fwd": ("_alpha",),
                 "raster_bwd": ("_aa", "_alpha"), "camera_grad": ("_aa",)}
 
 
-def _stage_call(L, stage, opts, args, alpha=None):
+def _stage_call(L, stage, opts, args, alpha=None, absgrad=None):
     """fdgs_<stage> in the form `opts` selects, on `args`; `alpha`: the pointer of the alpha image (or of its gradient), for the forms that
-    take one."""
+    take one; `absgrad`: the pointer of the absolute screen-space gradients, for the backward of a frame that asked for them."""
+    if stage == "raster_bwd" and opts.absgrad:
+        check(L.fdgs_raster_bwd_abs(*args, alpha, 1 if opts.antialiasing else 0, absgrad))
+        return
     forms = _STAGE_FORMS[stage]
     form = "_aa" if opts.antialiasing and "_aa" in forms else "_alpha" if opts.alpha and "_alpha" in forms else ""
     if form and "_alpha" in forms:
@@ -204,7 +212,7 @@ def _none_if_empty(t):
 class RasterState:
     """Buffers one forward pass leaves behind for its backward (the reference's geom/binning/img buffers).  `capacity` = the pair count
     the binning buffer is laid out for (what the C calls take as num_rendered); `num_rendered` = the true count (waits for it if needed)."""
-    __slots__ = ("params", "geom", "binning", "img", "capacity", "count", "keep", "visibility", "acc", "with_alpha", "antialiasing")
+    __slots__ = ("params", "geom", "binning", "img", "capacity", "count", "keep", "visibility", "acc", "with_alpha", "antialiasing", "absgrad")
 
     def take_accumulator(self):
         """(buffer, zeroed) for fdgs_raster_grads::scratch_acc: the [P,16] accumulator the forward zero-filled on the way (training frames), once;
@@ -220,9 +228,9 @@ class RasterState:
 
     @property
     def options(self):
-        """The FrameOptions this frame was rendered with.  Read from the two slots on every call: the backward and the camera gradient
+        """The FrameOptions this frame was rendered with.  Read from the three slots on every call: the backward and the camera gradient
         follow the state as it is when they run."""
-        return FrameOptions(self.with_alpha, self.antialiasing)
+        return FrameOptions(self.with_alpha, self.antialiasing, self.absgrad)
 
 
 def _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp):
@@ -287,17 +295,18 @@ def _finish_exact(L, st, p, geom, img, cnt, opts, color, depth, alpha):
 
 
 def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, out=None, expect_backward=False,
-                      want_alpha=False, antialiasing=False):
+                      want_alpha=False, antialiasing=False, absgrad=False):
     """Runs stages 1-4 of include/fdgs.h. Returns (color, radii, depth, state).  `out` = (color [3,H,W], radii [P] int32, depth [1,H,W])
     buffers to write into (contiguous float32 / int32 on the device), e.g. slices of a batch tensor.  `expect_backward`: a training frame
     (the blending forward zero-fills the backward's accumulator on the way).  Which binning path runs: BINNING above -- every mode but the
     opt-in "capacity" returns the exact path's image.  `want_alpha` and `antialiasing` are the frame's FrameOptions: with `want_alpha` the
     result is (color, radii, depth, alpha [1,H,W], state), `out` has the alpha buffer as its fourth entry and the backward of `state` takes
     the alpha image's gradient (rasterize_backward's grad_alpha); with `antialiasing` every opacity is compensated (opacity * h,
-    include/fdgs.h).  Both are recorded on `state`, whose backward and camera gradient follow it; which entry point each stage calls:
-    _stage_call.  A frame that does not ask makes the C calls it always made."""
+    include/fdgs.h); with `absgrad` the forward is the one it would be without and the backward of `state` also returns the absolute
+    screen-space gradients (rasterize_backward's means2D_abs).  All are recorded on `state`, whose backward and camera gradient follow it;
+    which entry point each stage calls: _stage_call.  A frame that does not ask makes the C calls it always made."""
     global capacity_reruns
-    opts = FrameOptions(bool(want_alpha), bool(antialiasing))
+    opts = FrameOptions(bool(want_alpha), bool(antialiasing), bool(absgrad))
     L = _lib.lib()
     dev = means3D.device
     if not _is_hip_device(dev):
@@ -349,7 +358,7 @@ def rasterize_forward(settings, means3D, shs, colors_precomp, opacities, scales,
     state = RasterState()
     state.params, state.geom, state.binning, state.img, state.capacity, state.count = p, geom, binning, img, cap, cnt
     state.visibility, state.acc, state.keep = vis, acc, tensors
-    state.with_alpha, state.antialiasing = opts
+    state.with_alpha, state.antialiasing, state.absgrad = opts
     if opts.alpha:
         return color, radii, depth, alpha, state
     return color, radii, depth, state
@@ -367,11 +376,15 @@ def fill_raster_grads(state, grad_color, grad_depth, d_means2D, epilogue=None):
     return g, acc
 
 
-def raster_bwd_call(L, state, g, grad_alpha=None):
+def raster_bwd_call(L, state, g, grad_alpha=None, means2D_abs=None):
     """fdgs_raster_bwd of `state` on the filled fdgs_raster_grads `g`, in the form state.options selects (_stage_call).  `grad_alpha`
-    [1,H,W] (contiguous float32): the gradient of the alpha image of a frame rendered with it, NULL where alpha did not reach the loss."""
+    [1,H,W] (contiguous float32): the gradient of the alpha image of a frame rendered with it, NULL where alpha did not reach the loss.
+    `means2D_abs` [P,3] (contiguous float32): where an absgrad state's backward writes the absolute screen-space gradients; such a state
+    must be given one (a NULL would silently be the call of a frame that did not ask)."""
+    if state.absgrad and means2D_abs is None:
+        raise _lib.FdgsError("the backward of a frame rendered with absgrad needs the means2D_abs buffer")
     _stage_call(L, "raster_bwd", state.options, (stream_ptr(), state.params, ptr(state.geom), ptr(state.binning), ptr(state.img), state.capacity, g),
-                ptr(grad_alpha if state.with_alpha else None))
+                ptr(grad_alpha if state.with_alpha else None), ptr(means2D_abs if state.absgrad else None))
 
 
 def camera_wants_grad(settings):
@@ -403,7 +416,9 @@ def split_camera_gradients(out48, viewmatrix, projmatrix, campos):
 def rasterize_backward(state, grad_color, grad_depth=None, camera=False, grad_alpha=None):
     """Backward of rasterize_forward. Returns dict of gradients (None where the input was absent).  `camera`: also the camera's gradient,
     as `viewmatrix` [4,4], `projmatrix` [4,4] and `campos` [3] (fdgs_camera_grad on the same accumulator, behind fdgs_raster_bwd).
-    `grad_alpha`: the gradient of the alpha image of a frame rendered with want_alpha (None: it did not reach the loss)."""
+    `grad_alpha`: the gradient of the alpha image of a frame rendered with want_alpha (None: it did not reach the loss).  A state rendered
+    with absgrad also returns `means2D_abs` [P,3]: per Gaussian the sum over the pixels of the absolute screen-space gradient, in the units of
+    `means2D`, third column 0 (include/fdgs.h at fdgs_raster_bwd_abs); any other state has no such key."""
     L = _lib.lib()
     p = state.params
     means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp = state.keep[:7]
@@ -420,7 +435,9 @@ def rasterize_backward(state, grad_color, grad_depth=None, camera=False, grad_al
     g, scratch = fill_raster_grads(state, grad_color, grad_depth, out["means2D"])
     g.dL_dmeans3D, g.dL_dopacity, g.dL_dcolors, g.dL_dcov3D = ptr(out["means3D"]), ptr(out["opacities"]), ptr(out["colors"]), ptr(out["cov3D"])
     g.dL_dsh, g.dL_dscales, g.dL_drotations = ptr(out["shs"]), ptr(out["scales"]), ptr(out["rotations"])
-    raster_bwd_call(L, state, g, grad_alpha)
+    if state.absgrad:
+        out["means2D_abs"] = torch.empty(P, 3, device=dev)
+    raster_bwd_call(L, state, g, grad_alpha, out.get("means2D_abs"))
     if camera:
         c = out["camera"] = camera_gradients(state, scratch)       # (the call's 48 floats; the three below are views of it)
         out.update(viewmatrix=c[:16].reshape(4, 4), projmatrix=c[16:32].reshape(4, 4), campos=c[32:35])
@@ -431,11 +448,19 @@ def rasterize_backward(state, grad_color, grad_depth=None, camera=False, grad_al
 # One forward and one backward body; each node class is the signature its frames record, around them.  Separate classes, so that a frame
 # that does not ask for the camera's gradient records the node, with the inputs, it always recorded.
 
-def _node_forward(ctx, raster_settings, gaussians, expect_backward, opts):
-    """`gaussians`: rasterize_forward's seven per-Gaussian inputs, in its order."""
+def leave_absgrad(sink, rows):
+    """The contract of an absgrad frame (gsplat's means2d.absgrad): the tensor the caller passed as means2D -- render()'s
+    result["viewspace_points"] -- gets the [P,3] float32 absolute screen-space gradients as its attribute `.absgrad`, ASSIGNED by every
+    backward of the frame, never accumulated (a statistic of one backward, not a gradient)."""
+    sink.absgrad = rows
+
+
+def _node_forward(ctx, raster_settings, gaussians, expect_backward, opts, means2D=None):
+    """`gaussians`: rasterize_forward's seven per-Gaussian inputs, in its order; `means2D`: the node's screen-space input."""
     _, sh, colors_precomp, opacities, scales, _, cov3Ds_precomp = gaussians
     *images, state = rasterize_forward(raster_settings, *gaussians, expect_backward=expect_backward, **opts.keywords())
     ctx.state = state
+    ctx.absgrad_sink = means2D if opts.absgrad else None      # (the caller's tensor: its backward leaves .absgrad there; no cycle, it is an input)
     ctx.had = (sh is not None and sh.numel() > 0, colors_precomp is not None and colors_precomp.numel() > 0,
                scales is not None and scales.numel() > 0, cov3Ds_precomp is not None and cov3Ds_precomp.numel() > 0)
     ctx.shapes = (opacities.shape, None if sh is None else sh.shape)
@@ -461,6 +486,8 @@ def _node_backward(ctx, grad_color, grad_depth, grad_alpha, cam_at=None):
     if grad_alpha is not None:
         kw["grad_alpha"] = grad_alpha
     g = rasterize_backward(ctx.state, grad_color, grad_depth, **kw)
+    if ctx.absgrad_sink is not None:
+        leave_absgrad(ctx.absgrad_sink, g["means2D_abs"])
     had_sh, had_col, had_scale, had_cov = ctx.had
     op_shape, sh_shape = ctx.shapes
     out[:8] = (g["means3D"], g["means2D"], g["shs"].reshape(sh_shape) if had_sh else None, g["colors"] if had_col else None,
@@ -476,7 +503,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, grad_mode=True,
                 opts=PLAIN):
         return _node_forward(ctx, raster_settings, (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp),
-                             bool(grad_mode) and any(ctx.needs_input_grad), opts)
+                             bool(grad_mode) and any(ctx.needs_input_grad), opts, means2D)
 
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha=None):
@@ -492,7 +519,8 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix, campos,
                 raster_settings, opts=PLAIN):
         ctx.cam = (viewmatrix, projmatrix, campos)        # (shape / dtype / device of the gradients to return; inputs of this node anyway)
-        return _node_forward(ctx, raster_settings, (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp), True, opts)
+        return _node_forward(ctx, raster_settings, (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp), True, opts,
+                             means2D)
 
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha=None):
@@ -500,10 +528,11 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, render_alpha=False,
-                        antialiasing=False):
+                        antialiasing=False, absgrad=False):
     """-> (color, radii, depth), with `render_alpha` (color, radii, depth, alpha).  `antialiasing`: every opacity is compensated for the
-    dilation of its footprint (rasterize_forward)."""
-    opts = FrameOptions(bool(render_alpha), bool(antialiasing))
+    dilation of its footprint (rasterize_forward).  `absgrad`: every backward of the frame leaves the absolute screen-space gradients on
+    `means2D` as `means2D.absgrad` (leave_absgrad)."""
+    opts = FrameOptions(bool(render_alpha), bool(antialiasing), bool(absgrad))
     if camera_wants_grad(raster_settings):
         rs = raster_settings
         return _RasterizeGaussiansCamera.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -518,6 +547,9 @@ class GaussianRasterizer(nn.Module):
     # instance, `rasterizer.antialiasing = True`.  An attribute, not a constructor argument: the constructor's parameter list is pinned
     # (tests/test_alpha_abi.py); rasterize_gaussians takes it as a keyword.
     antialiasing = False
+    # Opt-in absolute screen-space gradients (AbsGS; gsplat's absgrad), set the same way: `rasterizer.absgrad = True`, then read
+    # `means2D.absgrad` [P,3] of the tensor passed as means2D after a backward.
+    absgrad = False
 
     def __init__(self, raster_settings, render_alpha=False):
         """`render_alpha`: forward also returns the accumulated opacity of every pixel, alpha [1,H,W] = 1 - final transmittance,

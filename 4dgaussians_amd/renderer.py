@@ -2,7 +2,8 @@
 
 Same signature, same result dict {"render","viewspace_points","visibility_filter","radii","depth"} (and, opt-in through
 `pipe.render_alpha = True`, "alpha": the accumulated opacity [1,H,W], differentiable; `pipe.antialiasing = True` compensates every opacity
-for the 0.3 px dilation of its footprint, upstream's `antialiasing`); honours
+for the 0.3 px dilation of its footprint, upstream's `antialiasing`; `pipe.absgrad = True` leaves the absolute screen-space gradients of every
+backward on the frame's "viewspace_points" as `.absgrad` [P,3], the densification statistic of AbsGS); honours
 pipe.convert_SHs_python / pipe.compute_cov3D_python / pipe.debug and cam_type == "PanopticSports" exactly where the
 reference does.  When `pc._deformation` is this package's `deform_network`, the fine stage runs as two fused HIP
 stages: deform(+activations, + the cat of features_dc/features_rest) -> rasterize; no `time.repeat(N,1)` tensor, no
@@ -111,13 +112,15 @@ def _fused_backward(states, saved, grad_colors, grad_depths, grad_alphas, camera
     accumulate), then that view's deformation backward -- same output pointers and scratch (stream-ordered reuse), its own saved activations.
     `camera`: per view also the 48 floats of fdgs_camera_grad, run behind that view's fdgs_raster_bwd on its accumulator.  `time`: per view
     also the [1] tensor of fdgs_deform_time_grad, run behind that view's fdgs_deform_bwd.
-    Returns ([d means2D per view], the arena's views in _DeformFunction's input order, [camera rows per view], [time rows per view]); the
-    last two hold None where not asked for."""
+    Views rendered with absgrad also get their [P,3] absolute screen-space gradients (fdgs_raster_bwd_abs: the same launches).
+    Returns ([d means2D per view], the arena's views in _DeformFunction's input order, [camera rows per view], [time rows per view],
+    [absolute rows per view]); the last three hold None where not asked for."""
     L, stream = _lib.lib(), _lib.stream_ptr()
     st0 = states[0][0]
     b = _deformation.backward_prepare(st0, saved[0], saved[1], saved[2], identity_assigned=EPILOGUE_ASSIGN, zero_by_epilogue=zero_by_epilogue)
     dev = b.d_xyz.device
     g_means2D, cam_rows, time_rows, keep = [None] * len(states), [None] * len(states), [None] * len(states), []
+    abs_rows = [None] * len(states)
     for k_, v in enumerate(reversed(range(len(states)))):
         st, rstate = states[v]
         p = rstate.params
@@ -127,7 +130,9 @@ def _fused_backward(states, saved, grad_colors, grad_depths, grad_alphas, camera
         gm = g_means2D[v] = torch.empty(p.P, 3, device=dev)
         epi = _fill_epilogue(st, b, EPILOGUE_ASSIGN and k_ == 0)
         g, acc = _rasterizer.fill_raster_grads(rstate, gc, gd, gm, epi)      # (acc: zero-filled by the blending forward of this frame, no fill launch here)
-        _rasterizer.raster_bwd_call(L, rstate, g, ga)
+        if rstate.absgrad:
+            abs_rows[v] = torch.empty(p.P, 3, device=dev)
+        _rasterizer.raster_bwd_call(L, rstate, g, ga, abs_rows[v])
         if camera:
             cam_rows[v] = _rasterizer.camera_gradients(rstate, acc)
         b.g.out_scales, b.g.out_rotations, b.g.out_opacity = _lib.ptr(saved[3 * v]), _lib.ptr(saved[3 * v + 1]), _lib.ptr(saved[3 * v + 2])
@@ -138,7 +143,7 @@ def _fused_backward(states, saved, grad_colors, grad_depths, grad_alphas, camera
         if time:
             time_rows[v] = _deformation.time_gradient(st, b)
         keep.append((gc, gd, ga, acc, epi))      # (what the queued launches read lives until the last of them is queued)
-    return g_means2D, _deformation.gradient_tuple(st0, b), cam_rows, time_rows
+    return g_means2D, _deformation.gradient_tuple(st0, b), cam_rows, time_rows, abs_rows
 
 
 def _view_forward(cfg, opts, t_scalar, raster_settings, tensors, want, out=None):
@@ -157,9 +162,17 @@ def _view_forward(cfg, opts, t_scalar, raster_settings, tensors, want, out=None)
 # them.  Separate classes, so that a frame whose camera or time does not ask for a gradient records the node, with the inputs, it always
 # recorded -- autograd.Function.apply has a per-input cost (render(): the no-grad branch) -- and makes the C calls it always made.
 
+def _absgrad_sinks(cfg, opts):
+    """Where the backward of an absgrad frame leaves its rows: (the views' gradient sinks as the caller holds them, the permutation the set
+    was read through or None), put into the frame's own `cfg` by render() / render_views() -- the node's inputs are the PERMUTED sinks
+    where the implicit order is on, and the rows have to reach the caller's leaves in the model's row order."""
+    return cfg.get("absgrad_sinks") if opts.absgrad else None
+
+
 def _node_forward(ctx, cfg, opts, t_scalar, raster_settings, tensors, want):
     st, (color, radii, depth, *alpha, rstate) = _view_forward(cfg, opts, t_scalar, raster_settings, tensors, want)
     ctx.states = [(st, rstate)]
+    ctx.absgrad_sinks = _absgrad_sinks(cfg, opts)
     ctx.save_for_backward(st.o_sc, st.o_rot, st.o_op)       # (see deformation._node_forward: no reference cycle through ctx)
     st.o_sc = st.o_rot = st.o_op = None
     vis = rstate.visibility                                 # radii > 0, written by the projection kernel itself
@@ -177,8 +190,14 @@ def _node_backward(ctx, image_grads, sink_at, cam_at=None, time_at=None, zero_by
     if all(g is None for g in image_grads):                 # no image reached the loss
         return tuple(out)
     camera = cam_at is not None and any(ctx.needs_input_grad[cam_at:cam_at + 3])
-    g_means2D, grads, cam_rows, time_rows = _fused_backward(ctx.states, ctx.saved_tensors, *image_grads, camera=camera, time=time_at is not None,
-                                                            zero_by_epilogue=zero_by_epilogue)
+    g_means2D, grads, cam_rows, time_rows, abs_rows = _fused_backward(ctx.states, ctx.saved_tensors, *image_grads, camera=camera,
+                                                                      time=time_at is not None, zero_by_epilogue=zero_by_epilogue)
+    if ctx.absgrad_sinks is not None:       # (back through the scatter the signed rows take in PermuteRows.backward: the model's row order)
+        sinks, perm = ctx.absgrad_sinks
+        if perm is not None:
+            abs_rows = _deformation.permute_rows(perm, abs_rows, scatter=True)
+        for sink, rows in zip(sinks, abs_rows):
+            _rasterizer.leave_absgrad(sink, rows)
     model_at = sink_at + len(g_means2D)
     out[sink_at:model_at] = g_means2D
     out[model_at:] = grads[:6] + grads[7:]                  # (grads[6]: the deformation's time tensor, no input of these nodes)
@@ -254,6 +273,7 @@ class _FusedRenderViewsFunction(torch.autograd.Function):
             st, (*_, rstate) = _view_forward(cfg, opts, times[v], settings_list[v], tensors, want, out=tuple(o[v] for o in outs))
             states.append((st, rstate))
         ctx.states = states
+        ctx.absgrad_sinks = _absgrad_sinks(cfg, opts)
         # the activated outputs each view's backward needs: through save_for_backward (no reference cycle through ctx)
         ctx.save_for_backward(*[t for st, _ in states for t in (st.o_sc, st.o_rot, st.o_op)])
         for st, _ in states:
@@ -284,7 +304,10 @@ def render_views(viewpoint_cameras, pc, pipe, bg_color, scaling_modifier=1.0, st
         return [render(c, pc, pipe, bg_color, scaling_modifier, None, stage, cam_type) for c in cams]
     sinks = [_zero_leaf(means3D) for _ in cams]
     cfg, perm, ins, net_ins = _fine_stage(pc, sinks)       # (the set in Hilbert order for this step where perm is not None)
-    colors, radii, depths, *alphas = _FusedRenderViewsFunction.apply(cfg, FrameOptions.of(pipe), times, settings, len(cams), *ins, *net_ins)
+    opts = FrameOptions.of(pipe)
+    if opts.absgrad:
+        cfg["absgrad_sinks"] = (sinks, perm)
+    colors, radii, depths, *alphas = _FusedRenderViewsFunction.apply(cfg, opts, times, settings, len(cams), *ins, *net_ins)
     if perm is not None:
         radii = torch.stack(_deformation.permute_rows(perm, [radii[v] for v in range(len(cams))], scatter=True))
     res = [{"render": colors[v], "viewspace_points": sinks[v], "visibility_filter": radii[v] > 0, "radii": radii[v], "depth": depths[v]}
@@ -338,12 +361,15 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     # a leaf's .grad is filled by AccumulateGrad directly (same values, same attribute, read the same way by the train loop)
     screenspace_points = _zero_leaf(means3D)
     raster_settings, frame_time = _frame_settings(viewpoint_camera, cam_type, bg_color, scaling_modifier, pc.active_sh_degree, device, pipe)
-    opts = FrameOptions.of(pipe)            # opt-in: "alpha" [1,H,W], the accumulated opacity, joins the result (differentiable); antialiasing
+    # opt-in: "alpha" [1,H,W], the accumulated opacity, joins the result (differentiable); antialiasing; absgrad (viewspace_points.absgrad)
+    opts = FrameOptions.of(pipe)
     time_leaf = _time_leaf(viewpoint_camera, cam_type)      # opt-in: the frame time as something to fit (None: every frame there was before)
     if ("fine" in stage and "coarse" not in stage and FUSED_BACKWARD and override_color is None and not pipe.compute_cov3D_python
             and not pipe.convert_SHs_python and isinstance(pc._deformation, _deformation.deform_network)):
         # deformation + rasterizer as one autograd node (see _FusedRenderFunction)
         cfg, perm, ins, net_ins = _fine_stage(pc, (screenspace_points,) if torch.is_grad_enabled() else ())
+        if opts.absgrad:
+            cfg["absgrad_sinks"] = ((screenspace_points,), perm)
         if cfg["grad"] and time_leaf is not None:
             rs = raster_settings
             rendered_image, radii, depth, vis, *alpha = _FusedRenderTimeFunction.apply(cfg, opts, frame_time, rs, time_leaf, rs.viewmatrix,
@@ -415,6 +441,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     rasterizer = GaussianRasterizer(raster_settings=raster_settings, render_alpha=opts.alpha)       # (an nn.Module: only built on the paths that call it)
     if opts.antialiasing:
         rasterizer.antialiasing = True
+    if opts.absgrad:
+        rasterizer.absgrad = True
     rendered_image, radii, depth, *alpha = rasterizer(
         means3D=means3D_final, means2D=means2D, shs=shs_final, colors_precomp=colors_precomp, opacities=opacity_final,
         scales=scales_final, rotations=rotations_final, cov3D_precomp=cov3D_precomp)

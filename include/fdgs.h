@@ -262,6 +262,26 @@ int fdgs_camera_grad_host_aa(const fdgs_raster_params* p, const uint32_t* tiles,
                              const float* d_xy, const float* d_conic, const float* d_rgb, const float* d_depth, const float* d_opacity,
                              double* out /* 48 */);
 
+/* Absolute screen-space gradients (the "absgrad" of AbsGS, gsplat's means2d.absgrad): the densification statistic that does not cancel.
+ * dL_dmeans2D is the SIGNED sum over the pixels that blended a Gaussian; for a Gaussian that is too large the pixels on either side of its
+ * centre pull in opposite directions and the sum cancels, so the splats that most need splitting never reach the threshold.  For Gaussian i,
+ * with the loss gradient reaching the frame through colour, depth and (where given) alpha:
+ *       abs_i = ( sum_p |dL_p/dx_i| W/2 ,  sum_p |dL_p/dy_i| H/2 ,  0 )
+ * p runs over the pixels that blended i -- the `valid` decisions of the signed sum: inside n_contrib, power <= 0, alpha >= 1/255 --, and
+ * dL_p/d(x, y) is that pixel's WHOLE contribution to slots 0 and 1 of the accumulator line: summed over the three image gradients first,
+ * then taken absolute.  The scaling to NDC units is the one of dL_dmeans2D (a positive factor: it commutes with the absolute value).  Rows
+ * that are culled or that no pixel blended are exactly +0, the third column is exactly 0.  On an antialiased frame the per-pixel gradient is
+ * the one that frame's blending backward forms; nothing else is needed.
+ *   fdgs_raster_bwd_abs is fdgs_raster_bwd_alpha (antialiased = 0) or fdgs_raster_bwd_aa (antialiased != 0) of the same arguments, which
+ *   also writes dL_dmeans2D_abs [P,3] floats (4-byte aligned), every row.  The blending backward adds the two absolute sums into slots 10
+ *   and 11 of the Gaussian's scratch_acc line (same reductions, same atomic line-op; slots 12..15 stay zero), the per-Gaussian chain rule
+ *   writes them out, with the deformation epilogue as without.  Every other output is what the sibling call writes.
+ *   dL_dmeans2D_abs = NULL IS the sibling call: the same implementation, the kernels of a frame that does not ask (slots 10..15 stay zero).
+ *   P = 0: nothing is written.  No pairs: zeros. */
+int fdgs_raster_bwd_abs(void* stream, const fdgs_raster_params* p, const void* geom, const void* binning, const void* img,
+                        uint32_t num_rendered, const fdgs_raster_grads* g, const float* dL_dalpha /* opt */,
+                        int antialiased, float* dL_dmeans2D_abs /* [P,3], 4-byte aligned */);
+
 /* Frustum test only (replaces _C.mark_visible): present[P] (uint8) = 1 where p_view.z > 0.2. */
 int fdgs_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                       uint8_t* present);
