@@ -226,8 +226,16 @@ SYMBOLS = {
                                      c_void_p, c_float, c_void_p, c_void_p]),
     "fdgs_render_features_bwd": (c_int, [c_void_p, POINTER(RasterParams), c_void_p, c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p,
                                          c_float, c_void_p, c_int, c_void_p, c_int]),
+    # MCMC densification, host side (csrc/mcmc.hip): the arithmetic of csrc/mcmc_ops.h over host arrays
+    "fdgs_mcmc_philox_host": (c_int, [c_int, c_void_p, c_uint32, c_uint32, c_void_p]),
+    "fdgs_mcmc_weights_host": (c_int, [c_int, c_void_p, c_float, c_void_p, c_void_p]),
+    "fdgs_mcmc_sample_host": (c_int, [c_int, c_void_p, c_int, c_uint32, c_uint32, c_void_p, c_void_p]),
+    "fdgs_mcmc_relocation_host": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
+    "fdgs_mcmc_normals_host": (c_int, [c_int, c_uint32, c_uint32, c_void_p]),
+    "fdgs_mcmc_noise_host": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_uint32, c_uint32, c_void_p]),
 }
 CURVES = {"hilbert": 0, "morton": 1}      # FDGS_CURVE_*
+MCMC_TAGS = {"relocate": 0x52454C4F, "grow": 0x47524F57, "noise": 0x4E4F4953}      # FDGS_MCMC_TAG_*
 RGB8_MODES = {"trunc": 0, "round": 1}     # FDGS_RGB8_*
 PLACE_MODES = {"points": 0, "rigid": 1}   # FDGS_PLACE_*
 

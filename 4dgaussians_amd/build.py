@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libfdgs.so")
 SOURCES = ["api.hip", "preprocess.hip", "binning.hip", "render.hip", "deform.hip", "regulation.hip", "adam.hip", "knn.hip", "loss.hip", "densify.hip",
-           "spatial.hip", "playback.hip", "compose.hip", "motion.hip"]
+           "spatial.hip", "playback.hip", "compose.hip", "motion.hip", "mcmc.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function",
          "-Rpass-analysis=kernel-resource-usage"]     # (registers / scratch / LDS per kernel -> build/<unit>.resources.txt)
 

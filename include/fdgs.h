@@ -963,6 +963,68 @@ int fdgs_render_features_bwd(void* stream, const fdgs_raster_params* p, const vo
                              const float* alpha_opt /* [H,W], required when min_alpha >= 0 */, float min_alpha,
                              const int32_t* row_map_opt, int rows, float* dvalues, int dvalue_stride);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * MCMC densification, host side (additions to ABI 6; no existing struct or signature changed): the arithmetic of the second
+ * densification strategy beside clone / split / prune -- 3DGS-MCMC (Kheradmand et al. 2024): dead Gaussians are RELOCATED onto live ones
+ * sampled by opacity, the set GROWS 5 % at a time up to an exact cap, and every iteration adds opacity-gated, covariance-shaped NOISE to
+ * the positions.  csrc/mcmc_ops.h holds one __host__ __device__ function per operation; the functions declared here evaluate them over
+ * HOST arrays, without a GPU.  The device kernels and the Python strategy are not part of the library yet.
+ * Neither the authors' code nor gsplat's MCMCStrategy is part of the reference tree: THE FORMULAS BELOW ARE THE SPECIFICATION
+ * (parity unpinned).  All quantities are canonical (undeformed).
+ *
+ * Per Gaussian x_o, x_s[3], q[4] are the raw parameters, o = sigmoid(x_o), s = exp(x_s), R(q) the rotation of the normalised quaternion.
+ *
+ * Dead.  A row is dead when 1 / (1 + expf(-x_o)) <= min_opacity in float32 (the expression of the prune plan; a NaN is dead too).
+ *
+ * Sampling: with replacement, probability proportional to opacity, over the live rows, exact and independent of any reduction order.
+ *   weight[i]  uint32: 0 for a dead row, else clamp(floor(o * 2^32), 1, 2^32 - 1)        (o in float32; o * 2^32 is exact)
+ *   scan[i]    uint64 inclusive sum of the weights; total = scan[N - 1]
+ *   draw k     (w0, w1, w2, w3) = Philox4x32-10(counter = (k, 0, 0, 0), key = (seed, tag)); u_k = w1 * 2^32 + w0;
+ *              r_k = mulhi64(u_k, total) = floor(u_k * total / 2^64); the source is the first row i with scan[i] > r_k.
+ *   tag        FDGS_MCMC_TAG_RELOCATE / FDGS_MCMC_TAG_GROW tell the two calls of one refinement apart (the noise has its own, below).
+ *   Philox4x32-10 is the generator of Salmon et al. (SC'11): ten rounds of
+ *     (c0, c1, c2, c3) <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)),  M0 = 0xD2511F53, M1 = 0xCD9E8D57,
+ *   the key raised by (0x9E3779B9, 0xBB67AE85) after every round.
+ *   Replicas with equal parameters and an equal seed draw the same sources without a broadcast.
+ *
+ * Relocation values of a source drawn c >= 1 times: ratio r = min(c + 1, FDGS_MCMC_MAX_RATIO),
+ *   o' = 1 - (1 - o)^(1/r)
+ *   D  = sum_{i=1..r} sum_{k=0..i-1} C(i-1, k) (-1)^k o'^(k+1) / sqrt(k+1)
+ *   s' = s o / D;   then o' is clamped to [min_opacity, 1 - 2^-23];   x_o' = log(o' / (1 - o')),  x_s' = log(s').
+ *   r Gaussians (o', s') at one place blend to the same central alpha, 1 - (1 - o')^r = o, and cover the same area under the alpha
+ *   profile as the one (o, s) did; r = 1 is the identity.  The sum alternates with binomials up to C(50, 25) = 1.3e14: the whole chain,
+ *   from the raw parameters to x_o' and x_s', is evaluated in DOUBLE and rounded to float32 once (binomials from a constant table; the
+ *   inner sums closed by sum_{i=k+1..r} C(i-1, k) = C(r, k+1)).  Where the lower clamp acts, x_o' is rounded UP by between 0.75 and
+ *   1.75 units, so that the float32 dead test does not call a row filled with it dead again.
+ *
+ * Noise: xyz += (R diag(s^2) R^T) xi * g * lr,  g = 1 / (1 + exp(k_gate (o - min_opacity))), evaluated in DOUBLE from the float32 inputs
+ *   and rounded by the final add (a float32 rotation matrix carries absolute errors of 2^-24 that the largest s^2 multiplies);
+ *   xi ~ N(0, I3): (w0 .. w3) = Philox4x32-10(counter = (row, iteration, 0, 0), key = (seed, FDGS_MCMC_TAG_NOISE));
+ *   (xi0, xi1) = sqrt(-2 ln u1) (cos, sin)(2 pi u2), u1 = (w0 + 1) 2^-32 (never 0), u2 = (w1 >> 8) 2^-24; xi2 = the cosine branch of
+ *   (w2, w3).  lr = noise_lr * lr_xyz is the caller's product.
+ *
+ * FDGS_E_INVALID with a message for a negative size or a NULL required pointer (and a scan without a live row); a size of 0 succeeds and
+ * touches nothing.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define FDGS_MCMC_TAG_RELOCATE 0x52454C4Fu /* "RELO" */
+#define FDGS_MCMC_TAG_GROW 0x47524F57u     /* "GROW" */
+#define FDGS_MCMC_TAG_NOISE 0x4E4F4953u    /* "NOIS" */
+#define FDGS_MCMC_MAX_RATIO 51
+/* words[i] = Philox4x32-10(counters[i], key = (key0, key1)) */
+int fdgs_mcmc_philox_host(int n, const uint32_t* counters /* [n,4] */, uint32_t key0, uint32_t key1, uint32_t* words /* [n,4] */);
+/* weights and their inclusive scan from raw opacities */
+int fdgs_mcmc_weights_host(int N, const float* opacity, float min_opacity, uint32_t* weights, uint64_t* scan);
+/* n draws over a scan; counts_opt[N] (zeroed first) receives the draws per source */
+int fdgs_mcmc_sample_host(int N, const uint64_t* scan, int n, uint32_t seed, uint32_t tag, int32_t* src_out, uint32_t* counts_opt /* [N] */);
+/* x_o', x_s' of n rows drawn counts[i] times each (0: ratio 1) */
+int fdgs_mcmc_relocation_host(int n, const float* opacity, const float* scaling /* [n,3] */, const uint32_t* counts, float min_opacity,
+                              float* opacity_out, float* scaling_out);
+/* the normals of rows 0 .. N-1 for (seed, iteration) */
+int fdgs_mcmc_normals_host(int N, uint32_t seed, uint32_t iteration, float* out /* [N,3] */);
+/* the noise step in place on xyz; normals_opt [N,3] replaces the generator's */
+int fdgs_mcmc_noise_host(int N, float* xyz, const float* scaling, const float* rotation, const float* opacity, float lr, float k_gate,
+                         float min_opacity, uint32_t seed, uint32_t iteration, const float* normals_opt);
+
 #ifdef __cplusplus
 }
 #endif
