@@ -70,6 +70,11 @@ class AdamTensor(Structure):
                 ("lr", c_float), ("step", c_int)]
 
 
+class AdamRowsTensor(Structure):     # fdgs_adam_rows_tensor: a [rows, row_len] tensor and its row mask (NULL: dense)
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("rows", c_size_t),
+                ("row_len", c_int), ("visible", c_void_p), ("lr", c_float), ("step", c_int)]
+
+
 NGROUPS = 6
 
 
@@ -183,6 +188,8 @@ SYMBOLS = {
     "fdgs_image_loss_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p]),
     "fdgs_plane_regulation": (c_int, [c_void_p, c_int, POINTER(RegPlane), c_float, c_void_p, c_void_p]),
     "fdgs_adam_step": (c_int, [c_void_p, c_int, POINTER(AdamTensor), c_double, c_double, c_double]),
+    "fdgs_adam_step_rows": (c_int, [c_void_p, c_int, POINTER(AdamRowsTensor), c_double, c_double, c_double, c_int]),
+    "fdgs_adam_step_rows_host": (c_int, [c_int, POINTER(AdamRowsTensor), c_double, c_double, c_double, c_int]),
     "fdgs_knn3_mean_dist2": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "fdgs_densification_stats": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "fdgs_densify_scratch_bytes": (c_int, [c_int, POINTER(c_size_t)]),

@@ -549,6 +549,26 @@ typedef struct fdgs_adam_tensor {
 int fdgs_adam_step(void* stream, int ntensors, const fdgs_adam_tensor* tensors /* host array */, double beta1, double beta2,
                    double eps);   /* doubles: 1 - beta and the bias corrections are formed in double like torch does */
 
+/* Sparse Adam: the same step over [rows, row_len] tensors with a per-tensor row mask (graphdeco's SparseGaussianAdam, gsplat's
+ * SelectiveAdam).  Row i with visible[i] != 0 gets exactly the arithmetic of fdgs_adam_step; every other row keeps param, exp_avg and
+ * exp_avg_sq bit for bit and its gradient is not looked at (a NaN there changes nothing).  visible == NULL: every row is stepped, so dense
+ * and masked tensors of one step share one launch (64 tensors per launch, as fdgs_adam_step).  bias_correction == 0: step_size = lr and
+ * sqrt(1 - beta2^t) = 1, the upstream kernels' form.  `step` counts calls per tensor, not visits per row.  Refused before anything is
+ * launched: NULL arrays, step < 1, row_len < 1, rows * row_len >= 2^32, arrays that are not 16-byte aligned; ntensors == 0 and
+ * rows == 0 are no-ops.  fdgs_adam_step_rows_host: the same over host arrays, without a GPU (the same per-element function). */
+typedef struct fdgs_adam_rows_tensor {
+    float* param; const float* grad; float* exp_avg; float* exp_avg_sq;
+    size_t rows;
+    int row_len;
+    const unsigned char* visible;   /* NULL = dense, [rows] otherwise */
+    float lr;
+    int step;
+} fdgs_adam_rows_tensor;
+int fdgs_adam_step_rows(void* stream, int ntensors, const fdgs_adam_rows_tensor* tensors /* host array */, double beta1, double beta2,
+                        double eps, int bias_correction);
+int fdgs_adam_step_rows_host(int ntensors, const fdgs_adam_rows_tensor* tensors, double beta1, double beta2, double eps,
+                             int bias_correction);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Scale initialisation: replaces simple_knn._C.distCUDA2 (un-vendored submodule submodules/simple-knn, .gitmodules:1-3;
  * call site scene/gaussian_model.py:148).  mean_dist2[i] = mean of the three smallest squared distances from point i
